@@ -11,8 +11,15 @@ generated once on rank 0 and broadcast over RCCL before timing; there is no
 collective inside the timed region.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4|c5|fd|lat]
-                  [--scaling strong|weak] [--host-path]
+                  [--scaling strong|weak] [--host-path] [--full] [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline figure and
+the roofline arithmetic that needs no run of its own.  `--full` adds everything that takes
+further runs: the CPU baseline, the no-prefix comparison, the per-phase events, C1's host
+path, the multi-GPU ABI check at N > 1 and the oracle samples (`--no-cpu` / `--no-compare`
+still drop their part of it).  `--dump-outputs DIR` writes what the last timed step computed
+as DIR/<name>.npy (float32, a fixed seeded sample of rows where the output is large).
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
 """
@@ -178,6 +185,35 @@ def zero_bits(xs: torch.Tensor, skip_bits: int = 0) -> int:
         if part:  # the partial byte's first `part` bits are covered by the prefix
             tot -= int(lut[c[:, full] >> (8 - part)].sum().item()) - (8 - part) * c.shape[0]
     return tot
+
+
+DUMP_BUDGET = 48_000_000  # bytes of float32 over all the arrays (and ranks) of one run: under 64 MB with headers
+
+
+def sample_rows(rows: int, keep: int, seed: int = 0xDCF0D) -> np.ndarray | None:
+    """Sorted, distinct row indices for --dump-outputs: one seeded pick from each of `keep` equal
+    strata of [0, rows); None when all the rows fit.  The same (rows, keep) gives the same rows."""
+    if rows <= keep:
+        return None
+    rng = np.random.default_rng(seed)
+    edge = np.arange(keep + 1, dtype=np.int64) * rows // keep
+    pick = edge[:-1] + (rng.random(keep) * (edge[1:] - edge[:-1])).astype(np.int64)
+    return np.minimum(pick, edge[1:] - 1)  # inside its stratum whatever the rounding
+
+
+def dump_outputs(path: str, arrays: dict, world: int = 1, rank: int = 0) -> None:
+    """--dump-outputs: every output array of the timed path (2-D, rows x bytes, on the device or the
+    host) as <path>/<name>.npy in float32 (rank r > 0: <name>.rank<r>.npy), whole when it fits its
+    share of DUMP_BUDGET, else the rows sample_rows picks."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET // (len(arrays) * world)
+    for name, a in arrays.items():
+        idx = sample_rows(a.shape[0], max(1, share // (4 * a.shape[1])))
+        if isinstance(a, torch.Tensor):
+            a = (a if idx is None else a[torch.from_numpy(idx).to(a.device)]).cpu().numpy()
+        elif idx is not None:
+            a = a[idx]
+        np.save(os.path.join(path, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a.astype(np.float32))
 
 
 def dist_setup(n_gpus: int, backend: str = "nccl", force: bool = False):
@@ -451,19 +487,23 @@ def run_eval(args, world, rank):
     mine = {}
     wall, kern_s = timed_loop(step, args.steps, args.warmup, world, local=mine)
     kern_s /= parties
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ys": ys, "ys1": ys1} if parties == 2 else {"ys": ys}, world, rank)
     dev_blocks = prg.last_eval_blocks()  # stream engine: AES blocks of the last launch, counted on the device
-    # one more (untimed) eval with phase events: this rank's table build vs walk split
-    prg.set_phase_timing(True)
-    d.eval_device(False, cwb, s0, xs, ys)
-    torch.cuda.synchronize()
-    table_ms, walk_ms, depth = prg.last_eval_phases()
-    prg.set_phase_timing(False)
+    table_ms, walk_ms, depth = None, None, pfx
+    if args.full:
+        # one more (untimed) eval with phase events: this rank's table build vs walk split
+        prg.set_phase_timing(True)
+        d.eval_device(False, cwb, s0, xs, ys)
+        torch.cuda.synchronize()
+        table_ms, walk_ms, depth = prg.last_eval_phases()
+        prg.set_phase_timing(False)
     rank_rec = {"rank": rank, "device": torch.cuda.current_device(), "points": m, "start": start,
                 "wall_s": mine["wall_s"], "kernel_ms": kern_s * 1e3, "table_ms": table_ms, "walk_ms": walk_ms,
                 "prefix_levels": depth, "key_broadcast_ms": ktime.get("key_broadcast_ms")}
     per_rank = gather_per_rank(world, rank_rec)
     no_prefix = None
-    if pfx and not args.no_compare:
+    if pfx and args.full and not args.no_compare:
         # the same batch without the shared-prefix table (each point walks all 8N levels)
         prg.set_prefix_levels(0)
         w0, k0 = timed_loop(step, args.steps, args.warmup, world)
@@ -478,7 +518,7 @@ def run_eval(args, world, rank):
     value = total_evals / wall
     check = slice_check(d, cwb, s0, ys, nb, lam, args, world, rank) if args.check else None
     abi_check = None
-    if rank == 0 and (world > 1 or args.abi_check):
+    if rank == 0 and ((world > 1 and args.full) or args.abi_check):
         prg_cls = dcf_amd.Aes128MatyasMeyerOseasPrg if args.prg == "mmo" else dcf_amd.Aes256HirosePrg
         abi_check = multi_gpu_abi_check(keys, nb, lam, prg_cls, d, cwb, s0,
                                         points=min(1 << 20, max(1, (1 << 30) // (lam * 8))))
@@ -577,21 +617,22 @@ def run_eval(args, world, rank):
         out["slice_check"] = check
     if abi_check is not None:
         out["multi_gpu_abi_check"] = abi_check
-    out["phases"] = {"table_ms": table_ms, "walk_ms": walk_ms, "prefix_levels": depth,
-                     "note": "rank 0, one untimed eval with phase events (dcf_prg_set_phase_timing)"}
+    if args.full:
+        out["phases"] = {"table_ms": table_ms, "walk_ms": walk_ms, "prefix_levels": depth,
+                         "note": "rank 0, one untimed eval with phase events (dcf_prg_set_phase_timing)"}
     if pg():
         out["per_rank"] = per_rank_summary(per_rank, args.steps)
         out["key_broadcast"] = {"ms": ktime.get("key_broadcast_ms"), "bytes": ktime.get("key_bytes"),
                                 "backend": args.dist_backend, "note": "once, before timing (outside the timed region)"}
     host_ys = None
-    if args.host_path or args.workload == "c1":
+    if args.host_path or (args.full and args.workload == "c1"):
         share = dcf_amd.cwb_to_share(cwb.cpu().numpy().tobytes(), nb, lam, [])
         sd = seeds.cpu().numpy()
         out["host_path"], host_ys = host_path(
             d, lambda b: dcf_amd.Share([sd[b].tobytes()], share.cws, share.cw_np1), xs, lam, parties,
             max(1, min(args.steps, 3)))
         out["host_path"]["matches_device_path"] = bool(np.array_equal(host_ys[0], ys.cpu().numpy()))
-    if rank == 0 and world == 1 and not args.no_cpu:  # cpu_baseline: rank 0 at N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:  # cpu_baseline: rank 0 at N=1 only
         ns = min(m, 1 << 26, max(4096, (1 << 30) // lam))  # at most ~1 GiB of outputs copied back
         xs_h = xs[:ns].cpu().numpy()
         ys_h = [ys[:ns].cpu().numpy()] + ([ys1[:ns].cpu().numpy()] if parties == 2 else [])
@@ -746,23 +787,54 @@ def run_c5(args, world, rank):
         if record:
             ev[3].record(stream)
 
-    # block counts on the device: party 0's eval alone, then party 1's (the last launch)
-    d.gen_batch_device(alpha, beta, s0, s1, dcf_amd.BoundState.LtBeta, cwb)
-    d.eval_multikey_device(False, cwb, s0, xs, P, y0)
-    torch.cuda.synchronize()
-    b0 = prg.last_eval_blocks()
+    b0 = 0
+    if args.full:
+        # block counts on the device: party 0's eval alone, then party 1's (the last launch)
+        d.gen_batch_device(alpha, beta, s0, s1, dcf_amd.BoundState.LtBeta, cwb)
+        d.eval_multikey_device(False, cwb, s0, xs, P, y0)
+        torch.cuda.synchronize()
+        b0 = prg.last_eval_blocks()
     mine = {}
     wall, step_s = timed_loop(step, args.steps, args.warmup, world, local=mine)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cwb": cwb.view(-1, 16), "y0": y0, "y1": y1}, world, rank)
     b1 = prg.last_eval_blocks()
-    # per-phase HIP-event times over the same number of steps (separate loop: events between phases)
-    for _ in range(args.steps):
+    evals = 2 * global_keys * P * args.steps
+    out = {"metric": "C5 batched gen + eval (both parties)", "value": evals / wall, "unit": "evals/s",
+           "keys_per_s": global_keys * args.steps / wall, "n_gpus": world, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True,
+           "scaling": args.scaling, "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+           "aes_blocks_per_s_reference_count": evals / wall * blocks_per_eval(nb, lam) + global_keys * args.steps / wall * 4 * 8 * nb,
+           "config": {"workload": f"C5: {global_keys} keys x {P} points ({K} keys on this GPU), N={nb}, "
+                                  f"lambda={lam}, batched gen + multi-key eval of both parties per step",
+                      "n_bytes": nb, "lambda": lam, "keys_per_gpu": K, "points_per_key": P}}
+    if args.full:
+        out.update(c5_roofline(step, phase, ev, args.steps, step_s, b0 + b1, K, P, nb, lam))
+    if pg():
+        recs = gather_per_rank(world, {"rank": rank, "keys": K, "key_start": kstart, "wall_s": mine["wall_s"],
+                                       "kernel_ms": step_s * 1e3, "gen_ms": phase[0] * 1e3 if args.full else None,
+                                       "eval_ms": (phase[1] + phase[2]) * 1e3 if args.full else None})
+        out["per_rank"] = per_rank_summary(recs, args.steps)
+    if args.check:
+        chk = c5_check(d, cwb, y0, y1, args, world, rank, nb, lam, P)
+        if chk is not None:
+            out["slice_check"] = chk
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:  # cpu_baseline: rank 0 at N=1 only
+        out["cpu_baseline"] = c5_cpu_baseline(keys, nb, lam, alpha, beta, s0, s1, xs, cwb, y0, y1, K, P,
+                                              args.cpu_seconds)
+    return out
+
+
+def c5_roofline(step, phase, ev, steps, step_s, eval_blocks, K, P, nb, lam):
+    """--full: C5's per-phase HIP-event times (a loop of its own over `steps` more steps, events
+    between the phases; fills `phase`) and the roofline fields of the line that need them.
+    eval_blocks: both parties' multi-key stream engine blocks, counted on the device."""
+    for _ in range(steps):
         step(record=True)
         torch.cuda.synchronize()
         for i in range(3):
-            phase[i] += ev[i].elapsed_time(ev[i + 1]) / 1e3 / args.steps
-    evals = 2 * global_keys * P * args.steps
+            phase[i] += ev[i].elapsed_time(ev[i + 1]) / 1e3 / steps
     gen_blocks = 4 * 8 * nb * K                  # k_gen16: A and B of both parties' PRG per level
-    eval_blocks = b0 + b1                        # multi-key stream engine, counted on the device
     n = 8 * nb
     cwb_b = dcf_amd.cwb_bytes(nb, lam, K)
     dig_b = K * n * 33                           # key-major digest (k_cw_keymajor): 32 B CW + 1 B t per level
@@ -773,46 +845,25 @@ def run_c5(args, world, rank):
     achieved = (gen_blocks + eval_blocks) / step_s
     eval_s = phase[1] + phase[2]
     traffic, traffic_src = traffic_fields("k_gen16+2*k_mk_prefix16+2*k_cw_keymajor+2*k_eval16_stream", K * P, nb, lam, 0, alg_bytes)
-    out = {"metric": "C5 batched gen + eval (both parties)", "value": evals / wall, "unit": "evals/s",
-           "keys_per_s": global_keys * args.steps / wall, "n_gpus": world, "steps": args.steps,
-           "warmup": args.warmup, "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True,
-           "scaling": args.scaling, "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-           "aes_blocks_per_s_reference_count": evals / wall * blocks_per_eval(nb, lam) + global_keys * args.steps / wall * 4 * n,
-           "aes_blocks_per_s_executed_per_gpu": (gen_blocks + eval_blocks) / step_s,
-           "config": {"workload": f"C5: {global_keys} keys x {P} points ({K} keys on this GPU), N={nb}, "
-                                  f"lambda={lam}, batched gen + multi-key eval of both parties per step",
-                      "n_bytes": nb, "lambda": lam, "keys_per_gpu": K, "points_per_key": P},
-           "phases_ms": {"gen": phase[0] * 1e3, "eval_party0": phase[1] * 1e3, "eval_party1": phase[2] * 1e3,
-                         "note": "HIP events on the launch stream; each eval includes its key-major CW digest "
-                                 "(k_cw_keymajor) — profiles/ has the per-kernel split"},
-           "key_traffic_GBps": key_bytes / step_s / 1e9,
-           "roofline": {"bound": "lds", "kernel": "k_gen16 + k_mk_prefix16 + k_cw_keymajor + k_eval16_stream<MULTI> (whole step)",
-                        "engine": "stream (multi-key)", "achieved": achieved / 1e9, "peak": peak / 1e9,
-                        "unit": "G AES-256 blocks/s", "frac": achieved / peak,
-                        "eval_only": {"achieved": eval_blocks / eval_s / 1e9, "frac": eval_blocks / eval_s / peak,
-                                      "executed_blocks_per_eval": eval_blocks / (2 * K * P),
-                                      "measured_ceiling": measured_ceiling(eval_blocks / eval_s)},
-                        "gen_only": {"achieved": gen_blocks / phase[0] / 1e9, "frac": gen_blocks / phase[0] / peak},
-                        "traffic": traffic, "traffic_source": traffic_src, "algorithmic_bytes": alg_bytes,
-                        "lds_clock_bound": lds_clock_bound("C5", step_s) if (K, nb) == (1 << 20, 16) else None,
-                        "kernel_ms": step_s * 1e3, "hbm_GBps": alg_bytes / step_s / 1e9,
-                        "executed_blocks_per_step": gen_blocks + eval_blocks,
-                        "note": "gen: 4 AES-256 blocks per level per key (k_gen16); eval: blocks the multi-key "
-                                "stream engine encrypts, counted on the device (B every level, A on left levels, "
-                                "minus reused B); peak = T-table LDS bound 87.8 G blocks/s"}}
-    if pg():
-        recs = gather_per_rank(world, {"rank": rank, "keys": K, "key_start": kstart, "wall_s": mine["wall_s"],
-                                       "kernel_ms": step_s * 1e3, "gen_ms": phase[0] * 1e3,
-                                       "eval_ms": (phase[1] + phase[2]) * 1e3})
-        out["per_rank"] = per_rank_summary(recs, args.steps)
-    if args.check:
-        chk = c5_check(d, cwb, y0, y1, args, world, rank, nb, lam, P)
-        if chk is not None:
-            out["slice_check"] = chk
-    if rank == 0 and world == 1 and not args.no_cpu:  # cpu_baseline: rank 0 at N=1 only
-        out["cpu_baseline"] = c5_cpu_baseline(keys, nb, lam, alpha, beta, s0, s1, xs, cwb, y0, y1, K, P,
-                                              args.cpu_seconds)
-    return out
+    return {"aes_blocks_per_s_executed_per_gpu": (gen_blocks + eval_blocks) / step_s,
+            "phases_ms": {"gen": phase[0] * 1e3, "eval_party0": phase[1] * 1e3, "eval_party1": phase[2] * 1e3,
+                          "note": "HIP events on the launch stream; each eval includes its key-major CW digest "
+                                  "(k_cw_keymajor) — profiles/ has the per-kernel split"},
+            "key_traffic_GBps": key_bytes / step_s / 1e9,
+            "roofline": {"bound": "lds", "kernel": "k_gen16 + k_mk_prefix16 + k_cw_keymajor + k_eval16_stream<MULTI> (whole step)",
+                         "engine": "stream (multi-key)", "achieved": achieved / 1e9, "peak": peak / 1e9,
+                         "unit": "G AES-256 blocks/s", "frac": achieved / peak,
+                         "eval_only": {"achieved": eval_blocks / eval_s / 1e9, "frac": eval_blocks / eval_s / peak,
+                                       "executed_blocks_per_eval": eval_blocks / (2 * K * P),
+                                       "measured_ceiling": measured_ceiling(eval_blocks / eval_s)},
+                         "gen_only": {"achieved": gen_blocks / phase[0] / 1e9, "frac": gen_blocks / phase[0] / peak},
+                         "traffic": traffic, "traffic_source": traffic_src, "algorithmic_bytes": alg_bytes,
+                         "lds_clock_bound": lds_clock_bound("C5", step_s) if (K, nb) == (1 << 20, 16) else None,
+                         "kernel_ms": step_s * 1e3, "hbm_GBps": alg_bytes / step_s / 1e9,
+                         "executed_blocks_per_step": gen_blocks + eval_blocks,
+                         "note": "gen: 4 AES-256 blocks per level per key (k_gen16); eval: blocks the multi-key "
+                                 "stream engine encrypts, counted on the device (B every level, A on left levels, "
+                                 "minus reused B); peak = T-table LDS bound 87.8 G blocks/s"}}
 
 
 def c5_cpu_baseline(keys, nb, lam, alpha, beta, s0, s1, xs, cwb, y0, y1, K, P, target_s):
@@ -900,6 +951,8 @@ def run_fd(args, world, rank):
     if pg():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ys": ys}, world, rank)
     value = npts * world * args.steps / wall
     # one PRG call per internal node of the tree: A, B (Hirose) or 4 AES-128 blocks (MMO)
     blocks = (4 if mmo else 2) * (npts - 1)
@@ -924,7 +977,7 @@ def run_fd(args, world, rank):
                         "note": (f"{4 if mmo else 2} AES blocks per internal node (both children from one PRG "
                                  f"call), about {4 if mmo else 2} per leaf, vs {4 if mmo else 2} x 8N per point "
                                  "for pointwise eval")}}
-    if rank == 0 and world == 1 and not args.no_cpu:  # cpu_baseline: rank 0 at N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:  # cpu_baseline: rank 0 at N=1 only
         from oracle import oracle as O
         P = (O.OracleMmoPrg if mmo else O.OraclePrg)(keys, lam)
         cw = cwb.cpu().numpy().tobytes()
@@ -991,10 +1044,21 @@ def run_latency(args, world, rank):
     def c_eval():
         check(lib.dcf_eval(h, nb, 0, _ptr(cwb), cwb.size, _ptr(s0_b), _ptr(xb), 1, _ptr(yb), lam))
 
-    gen_us = per_call(c_gen, iters)
     eval_us = per_call(c_eval, iters)
-    assert np.array_equal(cw_out, cwb), "dcf_gen bytes differ from DcfImpl.gen's"
     y_gpu = yb.reshape(1, lam).copy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": y_gpu})
+    out = {"metric": "benches/dcf.rs latency: one gen / one single-point eval per call (us)", "value": eval_us,
+           "unit": "us per single-point eval (host path)", "n_gpus": 1, "steps": iters, "warmup": iters // 10,
+           "ms_per_step": eval_us / 1e3, "higher_is_better": False, "scaling": "none", "vs_baseline": None,
+           "dtype": "u8", "data": "synthetic",
+           "config": {"workload": "LAT: benches/dcf.rs bench_gen / bench_eval, N=16, lambda=16, Aes256HirosePrg "
+                                  "(2 AES keys), one key, one point, host buffers", "n_bytes": nb, "lambda": lam},
+           "eval_us": eval_us}
+    if not args.full:
+        return out
+    gen_us = per_call(c_gen, iters)
+    assert np.array_equal(cw_out, cwb), "dcf_gen bytes differ from DcfImpl.gen's"
     py_gen_us = per_call(lambda: d.gen(f, s0s, dcf_amd.BoundState.LtBeta), max(20, iters // 4))
     py_eval_us = per_call(lambda: d.eval(False, share0, x), max(20, iters // 4))
 
@@ -1014,22 +1078,18 @@ def run_latency(args, world, rank):
     cpu_gen_us = per_call(lambda: O.gen(P, f.alpha, f.beta, s0s[0], s0s[1], 0), iters)
     cpu_eval_us = per_call(lambda: O.eval_(P, 0, ok, s0s[0], xs, nthreads=1), iters)
     match = bool(np.array_equal(np.asarray(y_gpu), O.eval_(P, 0, ok, s0s[0], xs, nthreads=1)))
-    return {"metric": "benches/dcf.rs latency: one gen / one single-point eval per call (us)", "value": eval_us,
-            "unit": "us per single-point eval (host path)", "n_gpus": 1, "steps": iters, "warmup": iters // 10,
-            "ms_per_step": eval_us / 1e3, "higher_is_better": False, "scaling": "none", "vs_baseline": None,
-            "dtype": "u8", "data": "synthetic",
-            "config": {"workload": "LAT: benches/dcf.rs bench_gen / bench_eval, N=16, lambda=16, Aes256HirosePrg "
-                                   "(2 AES keys), one key, one point, host buffers", "n_bytes": nb, "lambda": lam},
-            "gen_us": gen_us, "eval_us": eval_us, "python_api_gen_us": py_gen_us, "python_api_eval_us": py_eval_us,
-            "gen_with_prg_new_us": gen_fresh_us, "eval_with_prg_new_us": eval_fresh_us,
-            "cpu_baseline": {"gen_us": cpu_gen_us, "eval_us": cpu_eval_us, "cores": 1, "kind": "port",
-                             "sample": f"{iters} calls each, the C restatement with AES-NI, 1 thread",
-                             "matches_gpu": match},
-            "note": "latency-bound: a tiny call is ONE launch of a latency kernel (kernels_lat.h: the AES of a "
-                    "block on a 16-lane row; k_eval16_row2 — two levels per AES chain on right steps — / "
-                    "k_gen16_row) that reads the key and points from, and writes its outputs to, a mapped pinned "
-                    "buffer, plus one stream sync; a lone point's 8N levels run back to back (~0.5 us per level); "
-                    "batch the points (C1) for throughput"}
+    out.update({
+        "gen_us": gen_us, "python_api_gen_us": py_gen_us, "python_api_eval_us": py_eval_us,
+        "gen_with_prg_new_us": gen_fresh_us, "eval_with_prg_new_us": eval_fresh_us,
+        "cpu_baseline": {"gen_us": cpu_gen_us, "eval_us": cpu_eval_us, "cores": 1, "kind": "port",
+                         "sample": f"{iters} calls each, the C restatement with AES-NI, 1 thread",
+                         "matches_gpu": match},
+        "note": "latency-bound: a tiny call is ONE launch of a latency kernel (kernels_lat.h: the AES of a "
+                "block on a 16-lane row; k_eval16_row2 — two levels per AES chain on right steps — / "
+                "k_gen16_row) that reads the key and points from, and writes its outputs to, a mapped pinned "
+                "buffer, plus one stream sync; a lone point's 8N levels run back to back (~0.5 us per level); "
+                "batch the points (C1) for throughput"})
+    return out
 
 
 def json_stdout():
@@ -1075,20 +1135,26 @@ def parse_args(argv=None):
     ap.add_argument("--points", type=int, default=None)
     ap.add_argument("--keys", type=int, default=1 << 20)
     ap.add_argument("--n-bytes", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baseline, no-prefix comparison, "
+                         "per-phase events, C1's host path, the multi-GPU ABI check at N > 1, oracle samples")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32; a "
+                         "fixed seeded sample of rows where the output is large)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--eval-mode", type=int, default=0, choices=[0, 1, 4],
                     help="LAMBDA = 16 AES engine: 0 auto, 1 lockstep T-table, 4 stream")
     ap.add_argument("--prg", default="hirose", choices=["hirose", "mmo"],
                     help="hirose: the reference's Aes256HirosePrg; mmo: Aes128MatyasMeyerOseasPrg (lambda = 16)")
     ap.add_argument("--prefix", type=int, default=-1,
                     help="shared-prefix table depth for single-key eval: -1 auto (library default), 0 off")
-    ap.add_argument("--no-compare", action="store_true", help="skip the no-prefix comparison timing")
+    ap.add_argument("--no-compare", action="store_true", help="with --full: skip the no-prefix comparison timing")
     ap.add_argument("--scaling", default=None, choices=["strong", "weak"],
                     help="strong: the workload's points (C5: keys) are split over the ranks (default for c3, c5); "
                          "weak: every rank gets the full count (default otherwise)")
     ap.add_argument("--host-path", action="store_true",
-                    help="also time dcf_eval on host buffers (PCIe included; always on for c1)")
+                    help="also time dcf_eval on host buffers (PCIe included; --full turns it on for c1)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo: CPU rehearsal)")
     ap.add_argument("--force-dist", action="store_true",
@@ -1097,7 +1163,7 @@ def parse_args(argv=None):
     ap.add_argument("--check", action="store_true",
                     help="after timing, rank 0 re-evaluates every rank's slice and compares output digests")
     ap.add_argument("--abi-check", action="store_true",
-                    help="run multi_gpu_abi_check at N = 1 too (always on at N > 1 for c1-c4)")
+                    help="run multi_gpu_abi_check at N = 1 too (--full turns it on at N > 1 for c1-c4)")
     args = ap.parse_args(argv)
     if args.scaling is None:
         args.scaling = "strong" if args.workload in ("c3", "c5") else "weak"

@@ -5,7 +5,7 @@
 # Sub-commands:
 #   suite   [pytest args]           GPU suite (-m gpu, or the given tests) + smoke()
 #   bench   W... [-- bench args]    bench lines of workloads W (c1 c2 c3 c4 c5 fd lat mmo; "all");
-#                                   c3 runs as the driver runs it (--gpus 1 --steps 20 --warmup 5)
+#                                   --full lines; c3 with the driver's steps (--gpus 1 --steps 20 --warmup 5)
 #   trace                           C3 bench line + a rocprofv3 kernel trace of the same workload in the
 #                                   same lease, reduced by scripts/lease_c3.py to prof_c3.md
 #   profile W [bench args]          kernel trace + FETCH_SIZE / WRITE_SIZE / SQ PMC passes (one pass
@@ -66,7 +66,7 @@ bench)
   WS=(); while [ $# -gt 0 ] && [ "$1" != -- ]; do WS+=("$1"); shift; done; [ "$1" = -- ] && shift
   [ "${WS[0]}" = all ] && WS=(c3 c1 c2 c4 c5 fd lat mmo)
   for w in "${WS[@]}"; do
-    timeout -k 10 600 python bench.py $(steps_of $w) "$@" > $O/bench_$w.json 2> $O/bench_$w.err \
+    timeout -k 10 600 python bench.py $(steps_of $w) --full "$@" > $O/bench_$w.json 2> $O/bench_$w.err \
       || { tail -20 $O/bench_$w.err; exit 1; }
     summary $O/bench_$w.json $w "" | tee -a $O/bench.txt
   done

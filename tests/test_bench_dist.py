@@ -24,7 +24,7 @@ def _free_port():
 def test_bench_two_ranks_strong_scaling_check():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--points", str((1 << 22) + 3), "--no-cpu",
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--points", str((1 << 22) + 3), "--full", "--no-cpu",
            "--no-compare", "--dist-backend", "gloo", "--check"]
     env = dict(os.environ, OMP_NUM_THREADS="4")
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
@@ -86,7 +86,7 @@ def test_bench_no_launcher_two_ranks_and_multi_gpu_abi():
     rank 0's one-process multi-GPU ABI check (dcf_eval_multi_gpu_device + gather) matches its
     own dcf_eval_device."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--points", str((1 << 22) + 3), "--no-cpu", "--no-compare", "--dist-backend", "gloo", "--check"]
+           "--points", str((1 << 22) + 3), "--full", "--no-cpu", "--no-compare", "--dist-backend", "gloo", "--check"]
     out = subprocess.run(cmd, cwd=ROOT, env=_no_launcher_env(), capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _one_line(out)
@@ -105,7 +105,7 @@ def test_bench_c5_two_ranks_check():
     digests; the per-rank block covers both ranks' keys."""
     keys = 4099
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--keys", str(keys), "--no-cpu", "--dist-backend", "gloo", "--check"]
+           "--warmup", "1", "--keys", str(keys), "--full", "--no-cpu", "--dist-backend", "gloo", "--check"]
     out = subprocess.run(cmd, cwd=ROOT, env=_no_launcher_env(), capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _one_line(out)
@@ -144,7 +144,8 @@ def test_bench_c4_two_ranks_check():
     compares output digests, and the one-process multi-GPU ABI check runs at LAMBDA = 16384."""
     pts = 4099
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c4", "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--points", str(pts), "--no-cpu", "--no-compare", "--dist-backend", "gloo", "--check"]
+           "--warmup", "1", "--points", str(pts), "--full", "--no-cpu", "--no-compare", "--dist-backend", "gloo",
+           "--check"]
     out = subprocess.run(cmd, cwd=ROOT, env=_no_launcher_env(), capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _one_line(out)

@@ -39,6 +39,34 @@ def test_wide_roofline_bound(bench):
     assert r["unit"] == "M evals/s" and r["bound"] == "lds+hbm"
 
 
+def test_dump_outputs_sample(bench, tmp_path):
+    # --dump-outputs: whole arrays when they fit, else a fixed, sorted, distinct row sample; float32
+    import numpy as np
+    import torch
+    assert bench.sample_rows(100, 100) is None
+    for rows, keep in ((101, 100), (1 << 28, 1 << 18), ((1 << 32) - 5, 750_000)):
+        idx = bench.sample_rows(rows, keep)
+        assert idx.shape == (keep,) and idx[0] >= 0 and idx[-1] < rows and (np.diff(idx) > 0).all()
+        assert np.array_equal(idx, bench.sample_rows(rows, keep))
+    rng = np.random.default_rng(5)
+    small = rng.integers(0, 256, (33, 16), dtype=np.uint8)
+    big = rng.integers(0, 256, (bench.DUMP_BUDGET // 64, 16), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path), {"small": torch.from_numpy(small), "big": big})
+    got = np.load(tmp_path / "small.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    got = np.load(tmp_path / "big.npy")
+    keep = bench.DUMP_BUDGET // 2 // 64
+    assert got.dtype == np.float32 and np.array_equal(got, big[bench.sample_rows(len(big), keep)])
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64_000_000
+
+
+def test_plain_run_is_the_default(bench):
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and a.dump_outputs is None and a.steps == 3 and a.workload == "c3"
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
 def test_zero_bits_below_prefix(bench):
     # the stream engine's A blocks: 0 bits of x below a shared prefix of `skip` levels
     import numpy as np

@@ -34,7 +34,7 @@ EXPORTS = [
     "dcf_share_bincode_bytes", "dcf_share_to_bincode", "dcf_share_from_bincode",
     "dcf_point_slice", "dcf_eval_multi_gpu", "dcf_eval_multi_gpu_device", "dcf_prg_set_prefix_max_bytes",
     "dcf_prg_device_bytes", "dcf_prg_host_pinned_bytes", "dcf_prg_workspaces", "dcf_prg_trim", "dcf_prg_set_phase_timing",
-    "dcf_prg_last_eval_phases",
+    "dcf_prg_last_eval_phases", "dcf_eval_range_device", "dcf_eval_range", "dcf_eval_range_subtree_levels",
 ]
 
 
@@ -86,6 +86,9 @@ def load(path: str = LIB_PATH):
         "dcf_eval_device": ([vp, sz, i, u8p, u8p, u8p, sz, u8p, vp], i),
         "dcf_eval_multikey_device": ([vp, sz, sz, sz, i, u8p, u8p, u8p, u8p, vp], i),
         "dcf_eval_full_domain_device": ([vp, sz, i, u8p, u8p, u8p, vp], i),
+        "dcf_eval_range_device": ([vp, sz, i, u8p, u8p, u8p, ctypes.c_uint64, u8p, vp], i),
+        "dcf_eval_range": ([vp, sz, i, u8p, sz, u8p, u8p, ctypes.c_uint64, u8p, sz], i),
+        "dcf_eval_range_subtree_levels": ([sz, ctypes.c_uint64], i),
         "dcf_share_bincode_bytes": ([sz, sz, sz], sz),
         "dcf_share_to_bincode": ([sz, sz, u8p, u8p, sz, u8p, sz], i),
         "dcf_share_from_bincode": ([sz, sz, u8p, sz, u8p, u8p, sz, ctypes.POINTER(sz)], i),

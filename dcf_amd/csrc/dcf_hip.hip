@@ -40,6 +40,7 @@
 #include "kernels_mmo.h"
 #include "kernels_mmo_wide.h"
 #include "kernels_wide_stream.h"
+#include "kernels_range.h"
 
 namespace {
 
@@ -2033,6 +2034,216 @@ int dcf_eval_full_domain_device(dcf_prg* p, size_t n_bytes, int party, const uin
     HIP_TRY(hipGetLastError());
   }
   return DCF_OK;
+}
+
+// ---- contiguous-range eval (kernels_range.h; DESIGN.md "Range eval") ----
+
+constexpr uint64_t kRangeDirectMax = 1ull << 12;  // counts below this walk every point (h = 0)
+constexpr uint64_t kRangeLaunch = 1ull << 28;     // outputs per launch group of the tree path (32-bit node and leaf indices)
+constexpr uint64_t kRangeChunk = 1ull << 22;      // points per pass of the materialising path
+
+// Height of the aligned blocks the tree path uses (the rule is documented in include/dcf_hip.h).
+static uint32_t range_levels(size_t n_bytes, uint64_t count) {
+  if (count < kRangeDirectMax) return 0;
+  const uint32_t lg = 63u - (uint32_t)__builtin_clzll(count);
+  const uint32_t h = std::min<uint32_t>(kRangeMaxH, std::max<uint32_t>(8u, lg - 8u));
+  return (uint32_t)std::min<uint64_t>(h, 8 * (uint64_t)n_bytes);
+}
+
+int dcf_eval_range_subtree_levels(size_t n_bytes, uint64_t count) {
+  return n_bytes ? (int)range_levels(n_bytes, count) : 0;
+}
+
+// x0 as the kernels take it: the low 16 bytes as a 128-bit value and the bytes above them.  Points
+// [0, first) of the range have top bytes `top`; the rest (only when the low 128 bits wrap, N > 16)
+// have `top1` = top + 1 and low bits counted from zero.
+struct RangeArg {
+  RangeX x;
+  RangeTop top, top1;
+  uint64_t first;
+};
+
+static int range_parse(size_t nb, const uint8_t* x0, uint64_t count, RangeArg* A) {
+  if (nb > 16 + kRangeTopMax) return fail(DCF_ERR_UNSUPPORTED, "range eval: N <= 256");
+  const size_t low = std::min<size_t>(nb, 16), nt = nb - low;
+  memset(A, 0, sizeof(*A));
+  memcpy(A->top.b, x0, nt);
+  for (size_t b = 0; b < low; ++b) {
+    const size_t pos = low - 1 - b;
+    const uint64_t v = x0[nt + b];
+    if (pos < 8) A->x.lo |= v << (8 * pos);
+    else A->x.hi |= v << (8 * (pos - 8));
+  }
+  A->first = count;
+  const RangeX last = range_add(A->x, count - 1);
+  const bool wrapped = last.hi < A->x.hi || (last.hi == A->x.hi && last.lo < A->x.lo);
+  const size_t bits = 8 * nb;
+  const bool fits = bits >= 128 || (bits <= 64 ? (last.hi == 0 && (bits == 64 || (last.lo >> bits) == 0))
+                                                : (last.hi >> (bits - 64)) == 0);
+  if (!fits || (wrapped && nt == 0)) return fail(DCF_ERR_ARG, "x0 + count exceeds 2^(8N)");
+  if (wrapped) {  // N > 16: the top bytes step once, after 2^128 - x (x.hi is all ones here)
+    A->top1 = A->top;
+    size_t b = nt;
+    while (b > 0 && ++A->top1.b[b - 1] == 0) --b;
+    if (b == 0) return fail(DCF_ERR_ARG, "x0 + count exceeds 2^(8N)");
+    A->first = 0 - A->x.lo;
+  }
+  return DCF_OK;
+}
+
+// Points [off, off + cnt) of the range as N-byte strings at xs.
+static int range_points(const RangeArg& A, size_t nb, uint64_t off, uint64_t cnt, uint8_t* xs, hipStream_t st) {
+  for (uint64_t done = 0; done < cnt;) {
+    const uint64_t i = off + done;
+    const bool hi = i >= A.first;
+    const uint64_t n = hi ? cnt - done : std::min<uint64_t>(cnt - done, A.first - i);
+    const RangeX x = hi ? RangeX{i - A.first, 0} : range_add(A.x, i);
+    hipLaunchKernelGGL(k_range_points, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
+                       (uint32_t)nb, x, hi ? A.top1 : A.top, n, xs + done * nb);
+    HIP_TRY(hipGetLastError());
+    done += n;
+  }
+  return DCF_OK;
+}
+
+// Points [off, off + cnt) of the range into ys (the output of point `off`), on L.st.  h: the
+// call's block height (range_levels of its whole count).  zero_blocks: first part of a call.
+static int range_launch(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
+                        const RangeArg& A, uint64_t off, uint64_t cnt, uint32_t h, uint8_t* ys, bool zero_blocks) {
+  hipStream_t st = L.st;
+  const size_t lam = p->lambda;
+  if (p->kind != 0 || lam != 16 || nb > 16) {  // no tree-sharing path: materialise the points, run eval
+    DevBuf xs;  // eval owns the workspace, so the points get their own buffer
+    const uint64_t chunk = std::min<uint64_t>(cnt, kRangeChunk);
+    HIP_TRY(xs.alloc(chunk * nb));
+    for (uint64_t o = 0; o < cnt; o += chunk) {
+      const uint64_t n = std::min<uint64_t>(chunk, cnt - o);
+      if (int rc = range_points(A, nb, off + o, n, (uint8_t*)xs.p, st)) return rc;
+      if (int rc = eval_launch(p, L, nb, 1, n, party, cwb, s0, (const uint8_t*)xs.p, ys + o * lam)) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(st));  // xs is freed on return
+    return DCF_OK;
+  }
+  Workspace* w = L.w;
+  if (int rc = ensure_ctr(w)) return rc;
+  const uint32_t nlev = (uint32_t)(8 * nb);
+  const uint64_t maxroots = (std::min<uint64_t>(cnt, kRangeLaunch) >> h) + 2;
+  const uint32_t m = h ? h - kRangeTail : 0u;  // breadth-first levels below a root
+  // two ping-pong buffers of rows (32 B) up to level 8N - kRangeTail (4 B per output of a launch
+  // in all), then one work counter per launch
+  const size_t buf_bytes = align256((maxroots * 32) << m), ctr_bytes = 16 * sizeof(uint32_t);
+  if (h)
+    if (int rc = ensure_ws(w, 2 * buf_bytes + ctr_bytes, st)) return rc;
+  if (zero_blocks) HIP_TRY(hipMemsetAsync(w->d_ctr, 0, kCtrBytes, st));
+  unsigned long long* blocks = reinterpret_cast<unsigned long long*>(w->d_ctr) + 1;
+  w->last_prefix = 0;
+  phase_mark(p, L, 0);
+  phase_mark(p, L, 1);
+  const uint4* cws = (const uint4*)cwb;
+  const uint4* cwv = (const uint4*)(cwb + (size_t)nlev * lam);
+  const uint8_t* cwt = cwb + 2 * (size_t)nlev * lam;
+  const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(nb, lam, 1));
+  const uint64_t cus = (uint64_t)p->cus;
+  if (h == 0) {  // every point is its own root: the root walk writes y
+    hipLaunchKernelGGL(k_range_roots16<true>, dim3((unsigned)std::min<uint64_t>(cus, (cnt + 31) / 32)), dim3(kBlock),
+                       0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, (const uint4*)s0, (uint32_t)party,
+                       range_add(A.x, off), nlev, cnt, (uint4*)ys, blocks);
+    HIP_TRY(hipGetLastError());
+  } else {
+    uint32_t* ctrs = (uint32_t*)(w->d_ws + 2 * buf_bytes);
+    for (uint64_t o = 0; o < cnt; o += kRangeLaunch) {
+      const uint64_t n = std::min<uint64_t>(kRangeLaunch, cnt - o);
+      const RangeX xa = range_add(A.x, off + o);
+      const uint64_t skip = xa.lo & ((1ull << h) - 1);
+      const RangeX pfx{(xa.lo >> h) | (xa.hi << (64 - h)), xa.hi >> h};
+      const uint64_t nroots = ((skip + n - 1) >> h) + 1;  // <= maxroots
+      uint4* cur = (uint4*)w->d_ws;
+      uint4* nxt = (uint4*)(w->d_ws + buf_bytes);
+      HIP_TRY(hipMemsetAsync(ctrs, 0, ctr_bytes, st));
+      hipLaunchKernelGGL(k_range_roots16<false>, dim3((unsigned)std::min<uint64_t>(cus, (nroots + 31) / 32)),
+                         dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, (const uint4*)s0,
+                         (uint32_t)party, pfx, nlev - h, nroots, cur, blocks);
+      HIP_TRY(hipGetLastError());
+      for (uint32_t k = 0; k < m; ++k) {  // level 8N - h + k: nroots << k parents
+        const uint64_t parents = nroots << k;
+        hipLaunchKernelGGL(k_range_level16, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
+                           p->rk[0], cws, cwv, cwt, nlev - h + k, (uint32_t)parents, (const uint4*)cur, nxt,
+                           ctrs + k, blocks);
+        HIP_TRY(hipGetLastError());
+        std::swap(cur, nxt);
+      }
+      const uint64_t nnodes = nroots << m;
+      hipLaunchKernelGGL(k_range_tail16<(int)kRangeTail>, dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock), 0,
+                         st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, nlev - kRangeTail, (uint32_t)nnodes,
+                         (const uint4*)cur, (uint32_t)skip, (uint32_t)n, (uint4*)(ys + o * lam), ctrs + 15, blocks);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  phase_mark(p, L, 2);
+  p->last_ws.store(w);
+  return DCF_OK;
+}
+
+int dcf_eval_range_device(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
+                          const uint8_t* x0, uint64_t count, uint8_t* ys, void* stream) {
+  if (!p) return fail(DCF_ERR_ARG, "null prg");
+  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
+  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
+  if (!cwb || !s0 || !x0) return fail(DCF_ERR_ARG, "null argument");
+  if (count == 0) return DCF_OK;
+  if (!ys) return fail(DCF_ERR_ARG, "null buffer");
+  RangeArg A;
+  if (int rc = range_parse(n_bytes, x0, count, &A)) return rc;
+  DeviceGuard dg(p->device);
+  Lease L(p);
+  if (int rc = L.order((hipStream_t)stream)) return rc;
+  return range_launch(p, L, n_bytes, party, cwb, s0, A, 0, count, range_levels(n_bytes, count), ys, true);
+}
+
+// The range over host buffers: chunks of outputs through the workspace's staging buffers on its
+// compute stream, one after the other (the key goes to the device once).
+static int host_range(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, size_t cwb_len,
+                      const uint8_t* s0, const RangeArg& A, uint64_t count, uint8_t* ys) {
+  Workspace* w = L.w;
+  const size_t lam = p->lambda;
+  const uint64_t chunk = std::min<uint64_t>(count, std::max<uint64_t>(256, kHostChunkBytes / lam));
+  const size_t kb = align256(cwb_len) + align256(lam), yb = align256(chunk * lam);
+  if (int rc = ensure_stage(w, yb, kb + yb)) return rc;
+  uint8_t* dk = w->d_stage;
+  uint8_t* ds0 = dk + align256(cwb_len);
+  uint8_t* dy = dk + kb;
+  HIP_TRY(hipMemcpyAsync(dk, cwb, cwb_len, hipMemcpyHostToDevice, L.st));
+  HIP_TRY(hipMemcpyAsync(ds0, s0, lam, hipMemcpyHostToDevice, L.st));
+  const uint32_t h = range_levels(nb, count);
+  for (uint64_t off = 0; off < count; off += chunk) {
+    const uint64_t n = std::min<uint64_t>(chunk, count - off);
+    if (int rc = range_launch(p, L, nb, party, dk, ds0, A, off, n, h, dy, off == 0)) return rc;
+    HIP_TRY(hipMemcpyAsync(w->h_stage, dy, n * lam, hipMemcpyDeviceToHost, L.st));
+    HIP_TRY(hipStreamSynchronize(L.st));
+    memcpy(ys + off * lam, w->h_stage, n * lam);
+  }
+  return DCF_OK;
+}
+
+int dcf_eval_range(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, size_t cwb_len, const uint8_t* s0,
+                   const uint8_t* x0, uint64_t count, uint8_t* ys, size_t ys_len) {
+  if (!p || !cwb || !s0 || !x0) return fail(DCF_ERR_ARG, "null argument");
+  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
+  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
+  const size_t lam = p->lambda;
+  if (cwb_len != dcf_cwb_bytes(n_bytes, lam, 1))
+    return fail(DCF_ERR_KEY, "key size does not match 8*N levels (lib.rs:165)");
+  if (ys_len % lam != 0 || ys_len / lam != count) return fail(DCF_ERR_LEN, "ys length != count * lambda");
+  if (count == 0) return DCF_OK;
+  if (!ys) return fail(DCF_ERR_ARG, "null buffer");
+  RangeArg A;
+  if (int rc = range_parse(n_bytes, x0, count, &A)) return rc;
+  DeviceGuard dg(p->device);
+  if (!dg.ok) return fail(DCF_ERR_HIP, "hipSetDevice failed");
+  Lease L(p);
+  int rc = host_lease(L);
+  if (rc == DCF_OK) rc = host_range(p, L, n_bytes, party, cwb, cwb_len, s0, A, count, ys);
+  return host_finish(L, rc);
 }
 
 int dcf_gen(dcf_prg* p, size_t n_bytes, const uint8_t* alpha, const uint8_t* beta, const uint8_t* s0_0,

@@ -387,6 +387,60 @@ class DcfImpl:
         check(_lib.load().dcf_eval_full_domain_device(self.prg.handle, nb, int(bool(b)), pk, ps, py, _stream(dev)))
         return ys
 
+    # ---- contiguous-range eval: Dcf::eval over x0, x0 + 1, ..., x0 + count - 1 ----
+    def _x0(self, x0) -> bytes:
+        """x0 as N big-endian bytes (lib.rs:181 reads a point Msb0)."""
+        nb = self.n_bytes
+        if isinstance(x0, int):
+            if x0 < 0 or x0 >> (8 * nb):
+                raise DcfError(-1, f"x0 = {x0} is outside [0, 2^{8 * nb})")
+            return x0.to_bytes(nb, "big")
+        x0 = bytes(x0)
+        if len(x0) != nb:
+            raise ValueError("x0 of the wrong length")
+        return x0
+
+    def range_subtree_levels(self, count: int) -> int:
+        """Height h of the aligned blocks the tree path of eval_range expands for `count` points
+        (dcf_eval_range_subtree_levels; the rule is in include/dcf_hip.h)."""
+        return int(_lib.load().dcf_eval_range_subtree_levels(self.n_bytes, int(count)))
+
+    def eval_range_device(self, b: bool, cwb, s0, x0, count: int, ys=None):
+        """`Dcf::eval` at x0 + i for i in [0, count) (x0: int or N big-endian bytes): the rows
+        eval_device returns over those points, as a (count, LAMBDA) device tensor.  Hirose
+        LAMBDA = 16: tree expansion, 2 AES blocks per output."""
+        import torch
+        lam, nb, dev = self.lam, self.n_bytes, self.prg.device
+        xb = self._x0(x0)
+        count = int(count)
+        if count < 0:
+            raise DcfError(-1, "count must not be negative")
+        pk = _dev(cwb, "cwb", dev, numel=cwb_bytes(nb, lam, 1))
+        ps = _dev(s0, "s0", dev, numel=lam)
+        if ys is None:
+            ys = torch.empty((count, lam), dtype=torch.uint8, device=cwb.device)
+        py = _dev(ys, "ys", dev, numel=count * lam)
+        check(_lib.load().dcf_eval_range_device(self.prg.handle, nb, int(bool(b)), pk, ps, _ptr(xb), count, py,
+                                                _stream(dev)))
+        return ys
+
+    def eval_range(self, b: bool, k: Share, x0, count: int, ys=None):
+        """Host buffers (dcf_eval_range): ys is a (count, LAMBDA) uint8 numpy array, overwritten in
+        place when given.  Returns ys."""
+        lam, nb = self.lam, self.n_bytes
+        cwb = share_to_cwb(k, nb, lam)
+        xb = self._x0(x0)
+        count = int(count)
+        if count < 0:
+            raise DcfError(-1, "count must not be negative")
+        if ys is None:
+            ys = np.zeros((count, lam), np.uint8)
+        if not (isinstance(ys, np.ndarray) and ys.dtype == np.uint8 and ys.flags["C_CONTIGUOUS"]):
+            raise TypeError("ys must be a contiguous uint8 numpy array")
+        check(_lib.load().dcf_eval_range(self.prg.handle, nb, int(bool(b)), _ptr(cwb), len(cwb),
+                                         _ptr(bytes(k.s0s[0])), _ptr(xb), count, _ptr(ys), ys.size))
+        return ys
+
 
 def point_slice(total: int, G: int, g: int):
     """dcf_point_slice: contiguous slice (start, count) of `total` points for slice g of G."""

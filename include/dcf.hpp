@@ -220,6 +220,27 @@ class DcfImpl final : public Dcf<N, LAMBDA> {
     check(dcf_eval(prg_.handle(), N, b ? 1 : 0, cwb.data(), cwb.size(), k.s0s[0].data(), xs, m, ys, m * LAMBDA));
   }
 
+  // Dcf::eval over the consecutive points x0 + i, i in [0, count) (x0 big-endian, lib.rs:181):
+  // ys = count * LAMBDA bytes, the rows eval returns for those points in order (dcf_eval_range:
+  // tree expansion, 2 AES blocks per output at LAMBDA = 16).  x0 + count may not exceed 2^(8N).
+  void eval_range(bool b, const Share<LAMBDA>& k, const std::array<uint8_t, N>& x0, uint64_t count,
+                  uint8_t* ys) const {
+    if (k.s0s.empty()) throw Error(DCF_ERR_KEY, "k.s0s is empty (lib.rs:168 reads s0s[0])");
+    const std::vector<uint8_t> cwb = share_to_cwb<N, LAMBDA>(k);
+    check(dcf_eval_range(prg_.handle(), N, b ? 1 : 0, cwb.data(), cwb.size(), k.s0s[0].data(), x0.data(), count, ys,
+                         (size_t)count * LAMBDA));
+  }
+
+  // Device form: cwb (single-key CWB), s0 and ys (count * LAMBDA bytes) on the prg's device,
+  // asynchronous on `stream` (dcf_eval_range_device); x0 is read before the call returns.
+  void eval_range_device(bool b, const uint8_t* cwb, const uint8_t* s0, const std::array<uint8_t, N>& x0,
+                         uint64_t count, uint8_t* ys, void* stream = nullptr) const {
+    check(dcf_eval_range_device(prg_.handle(), N, b ? 1 : 0, cwb, s0, x0.data(), count, ys, stream));
+  }
+
+  // Height of the aligned blocks eval_range expands for `count` points.
+  static int range_subtree_levels(uint64_t count) { return dcf_eval_range_subtree_levels(N, count); }
+
  private:
   const PrgT& prg_;
 };

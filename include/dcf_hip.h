@@ -296,6 +296,45 @@ int dcf_share_from_bincode(size_t n_bytes, size_t lambda, const uint8_t* in, siz
 int dcf_eval_full_domain_device(dcf_prg* prg, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
                                 uint8_t* ys, void* stream);
 
+/* Contiguous-range eval (the other half of SURVEY §8 f4): ys[i] = Dcf::eval(party, k, x0 + i) for
+ * i in [0, count), x0 + i the N-byte big-endian integer (Msb0, lib.rs:181) — the bytes
+ * dcf_eval_device returns over those points in that order, for any x0 and count (no alignment, no
+ * power of two), either PRG, every lambda, N <= 256.  cwb, s0 and ys (count * lambda bytes) are
+ * device pointers; x0 is a HOST pointer to n_bytes bytes, read before the call returns and passed
+ * to the kernels by value.  Asynchronous on `stream`.
+ *   Hirose PRG, lambda = 16, N <= 16: the range is covered by the aligned blocks of 2^h leaves that
+ *   intersect it (h = dcf_eval_range_subtree_levels); each block's root (level 8N - h) is walked
+ *   from s0 and its subtree expanded once, 2 AES blocks per output instead of 16N, and leaves
+ *   outside the range are not stored.  A call of more than 2^28 outputs runs as consecutive
+ *   launches of 2^28 each (node and leaf indices are 32-bit within a launch, 64-bit across them);
+ *   the workspace holds two buffers of the nodes four levels above the leaves, 4 B per output of
+ *   a launch in all.
+ *   dcf_prg_last_eval_blocks then reports the AES blocks of the root paths, the interior
+ *   expansion and the tail, clipped leaves of the edge blocks included.
+ *   Otherwise (MMO PRG, lambda >= 32, N > 16) the points are materialised on the device, 2^22 at a
+ *   time, and dcf_eval_device's path runs on them; that path waits for the stream before returning.
+ * Errors, nothing launched: x0 + count > 2^(8N) -> DCF_ERR_ARG; bad party / null pointer ->
+ * DCF_ERR_ARG; n_bytes == 0 -> DCF_ERR_N; N > 256 -> DCF_ERR_UNSUPPORTED.  count == 0 -> DCF_OK,
+ * nothing written. */
+int dcf_eval_range_device(dcf_prg* prg, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
+                          const uint8_t* x0, uint64_t count, uint8_t* ys, void* stream);
+
+/* The same over host buffers, synchronous: outputs come back in chunks of up to 128 MiB through the
+ * prg's staging pool on its compute stream.  ys_len != count * lambda -> DCF_ERR_LEN; cwb_len not
+ * one key's -> DCF_ERR_KEY (as dcf_eval). */
+int dcf_eval_range(dcf_prg* prg, size_t n_bytes, int party, const uint8_t* cwb, size_t cwb_len, const uint8_t* s0,
+                   const uint8_t* x0, uint64_t count, uint8_t* ys, size_t ys_len);
+
+/* Height h of the aligned blocks the tree path of dcf_eval_range* uses for this shape (pure
+ * arithmetic, no device access):
+ *   count < 2^12:  h = 0 — every point is walked on its own (32 lanes per point);
+ *   otherwise:     h = min(8N, 14, max(8, floor(log2(count)) - 8)).
+ * At least 2^8 blocks cover a range, so the root walk and the first levels below it have a few
+ * hundred nodes to spread over the CUs; h stops at 14: ten breadth-first levels (one launch each)
+ * above a 4-level register tail.  Root paths cost 2 (8N - h) / 2^h AES blocks per output (< 0.94 at N = 16), the two
+ * clipped edge blocks at most 4 * 2^h blocks in all. */
+int dcf_eval_range_subtree_levels(size_t n_bytes, uint64_t count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,4 +71,9 @@ extern "C" {
                                   s0s_out: *mut u8, max_s0s: usize, num_s0s: *mut usize) -> c_int;
     pub fn dcf_eval_full_domain_device(prg: *mut DcfPrg, n_bytes: usize, party: c_int, cwb: *const u8,
                                        s0: *const u8, ys: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn dcf_eval_range_device(prg: *mut DcfPrg, n_bytes: usize, party: c_int, cwb: *const u8, s0: *const u8,
+                                 x0: *const u8, count: u64, ys: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn dcf_eval_range(prg: *mut DcfPrg, n_bytes: usize, party: c_int, cwb: *const u8, cwb_len: usize,
+                          s0: *const u8, x0: *const u8, count: u64, ys: *mut u8, ys_len: usize) -> c_int;
+    pub fn dcf_eval_range_subtree_levels(n_bytes: usize, count: u64) -> c_int;
 }

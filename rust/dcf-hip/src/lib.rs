@@ -135,6 +135,25 @@ impl<const N: usize, const LAMBDA: usize> DcfHip<N, LAMBDA> {
         }
         Ok(())
     }
+
+    /// `Dcf::eval` over the consecutive points `x0 + i`, `i` in `[0, count)` (`x0` big-endian, as
+    /// lib.rs:181 reads a point): the rows `eval` returns for those points, in order, as one
+    /// `count * LAMBDA` byte vector (`dcf_eval_range`: tree expansion, 2 AES blocks per output at
+    /// `LAMBDA = 16`).  `x0 + count` may not exceed `2^(8N)`.
+    pub fn eval_range(&self, b: bool, k: &Share<LAMBDA>, x0: &[u8; N], count: u64) -> Result<Vec<u8>, DcfHipError> {
+        let cwb = share_to_cwb::<N, LAMBDA>(k);
+        let mut yb = vec![0u8; count as usize * LAMBDA];
+        check(unsafe {
+            ffi::dcf_eval_range(self.prg, N, b as c_int, cwb.as_ptr(), cwb.len(), k.s0s[0].as_ptr(), x0.as_ptr(),
+                                count, yb.as_mut_ptr(), yb.len())
+        })?;
+        Ok(yb)
+    }
+
+    /// Height of the aligned blocks `eval_range` expands for `count` points (`dcf_eval_range_subtree_levels`).
+    pub fn range_subtree_levels(count: u64) -> i32 {
+        unsafe { ffi::dcf_eval_range_subtree_levels(N, count) }
+    }
 }
 
 impl<const N: usize, const LAMBDA: usize> Dcf<N, LAMBDA> for DcfHip<N, LAMBDA> {

@@ -18,6 +18,8 @@
 #                                   one summary line per run appended to ab.txt
 #   abtest  VARIANT... [-- pytest args]  parity of each variant build on the GPU suite subset
 #   pmc     W "COUNTERS" [bench args]    one extra PMC pass (mean per dispatch per kernel printed)
+#   range   [range_bench args]      scripts/range_bench.py: range eval vs eval_device on the same points and
+#                                   vs full-domain eval at N = 4 -> range_bench.json (copy to profiles/)
 set -o pipefail
 export TMPDIR=/tmp
 TAG=$1; CMD=$2; shift 2
@@ -136,6 +138,23 @@ abtest)
       "$@" > $O/pytest_$v.log 2>&1 || { tail -60 $O/pytest_$v.log; exit 1; }
     echo "$v $(tail -1 $O/pytest_$v.log)"
   done
+  ;;
+range)  # contiguous-range eval vs the per-point route and full-domain eval: range [range_bench args]
+  timeout -k 10 900 python scripts/range_bench.py --out $O/range_bench.json "$@" > $O/range_bench.log 2> $O/range_bench.err \
+    || { tail -20 $O/range_bench.err; exit 1; }
+  python - $O/range_bench.json <<'PY'
+import json, sys
+d = json.load(open(sys.argv[1]))
+for r in d["ranges"]:
+    print("range N=%d count=2^%d h=%d %.4g out/s %.3f blocks/out lds=%.3f pointwise %.4g ev/s speedup %.1fx equal=%s" % (
+        r["n_bytes"], r["count"].bit_length() - 1, r["subtree_levels"], r["range_outputs_per_s"], r["blocks_per_output"],
+        r["lds_bound_frac"], r["pointwise_evals_per_s"], r["speedup"], r["outputs_equal"]))
+f = d.get("full_domain_n4")
+if f:
+    print("N=4 whole domain: range %.4g out/s, full-domain %.4g out/s (%.3f-%.3f ms), range/full %.3f, inside spread %s" % (
+        f["range_outputs_per_s"], f["full_domain_outputs_per_s"], f["full_domain"]["min_ms"], f["full_domain"]["max_ms"],
+        f["range_over_full_domain_ms"], f["range_inside_full_domain_spread"]))
+PY
   ;;
 *)
   echo "unknown sub-command $CMD"; exit 2;;

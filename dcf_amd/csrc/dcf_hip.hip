@@ -41,6 +41,7 @@
 #include "kernels_mmo_wide.h"
 #include "kernels_wide_stream.h"
 #include "kernels_range.h"
+#include "kernels_range_mk.h"
 
 namespace {
 
@@ -2244,6 +2245,163 @@ int dcf_eval_range(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, si
   int rc = host_lease(L);
   if (rc == DCF_OK) rc = host_range(p, L, n_bytes, party, cwb, cwb_len, s0, A, count, ys);
   return host_finish(L, rc);
+}
+
+// ---- multi-key contiguous-range eval (kernels_range_mk.h; DESIGN.md "Multi-key range eval") ----
+
+constexpr uint64_t kRangeMkDirectMax = 1ull << 12;  // fewer outputs than this in the whole call: h = 0
+
+// Height of the aligned blocks the multi-key tree path uses (documented in include/dcf_hip.h).
+static uint32_t rangemk_levels(size_t n_bytes, uint64_t num_keys, uint64_t count) {
+  if (count < (4ull << kRangeTail)) return 0;  // 2^h <= count / 4 needs h >= kRangeTail = 4
+  const uint64_t small = (kRangeMkDirectMax + count - 1) / count;  // K * count < 2^12 <=> K < ceil(2^12 / count)
+  if (num_keys < small) return 0;
+  const uint32_t lg = 63u - (uint32_t)__builtin_clzll(count);
+  const uint32_t h = std::min<uint32_t>(kRangeMaxH, lg - 2u);  // >= kRangeTail: count >= 64
+  return (uint32_t)std::min<uint64_t>(h, 8 * (uint64_t)n_bytes);
+}
+
+// Whole keys per launch group: every key has at most (count >> h) + 2 blocks of 2^h leaves.
+static uint64_t rangemk_keys_per_launch(uint32_t h, uint64_t count) {
+  const uint64_t maxroots = (count >> h) + 2;
+  if (maxroots > (kRangeLaunch >> h)) return 1;  // one key alone is more than a launch
+  return std::max<uint64_t>(1, kRangeLaunch / (maxroots << h));
+}
+
+int dcf_eval_range_multikey_subtree_levels(size_t n_bytes, size_t num_keys, uint64_t count) {
+  return n_bytes && num_keys ? (int)rangemk_levels(n_bytes, num_keys, count) : 0;
+}
+
+size_t dcf_eval_range_keys_per_launch(size_t n_bytes, size_t num_keys, uint64_t count) {
+  if (!n_bytes || !count) return 1;
+  return (size_t)rangemk_keys_per_launch(rangemk_levels(n_bytes, std::max<size_t>(num_keys, 1), count), count);
+}
+
+// One launch group of the tree path: keys [key0, key0 + keys) over the n <= 2^28 points from xa,
+// keys * n <= 2^28; the outputs of key key0 + k go to rows [k * n, (k + 1) * n) of ys (several keys
+// in a group: n is the call's count).
+static int rangemk_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb, const uint8_t* s0s,
+                         uint64_t key0, uint64_t keys, const RangeX xa, uint64_t n, uint32_t h, size_t buf_bytes,
+                         uint8_t* ys) {
+  hipStream_t st = L.st;
+  Workspace* w = L.w;
+  const size_t lam = 16;
+  const uint32_t nlev = (uint32_t)(8 * nb);
+  const uint4* cws = (const uint4*)cwb + key0;
+  const uint4* cwv = (const uint4*)(cwb + (size_t)nlev * K * lam) + key0;
+  const uint8_t* cwt = cwb + 2 * (size_t)nlev * K * lam + key0;
+  const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(nb, lam, K)) + key0;
+  const uint4* s0 = (const uint4*)s0s + key0;
+  unsigned long long* blocks = reinterpret_cast<unsigned long long*>(w->d_ctr) + 1;
+  const uint64_t cus = (uint64_t)p->cus;
+  if (h == 0) {  // every point is its own root: the root walk writes y
+    const uint64_t total = keys * n;
+    hipLaunchKernelGGL(k_rangemk_roots16<true>, dim3((unsigned)std::min<uint64_t>(cus, (total + 31) / 32)),
+                       dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, s0, (uint64_t)K, (uint32_t)party,
+                       xa, nlev, range_div_make((uint32_t)n), (uint32_t)total, (uint4*)ys, blocks);
+    HIP_TRY(hipGetLastError());
+    return DCF_OK;
+  }
+  const uint32_t m = h - kRangeTail;  // breadth-first levels below a root
+  const uint64_t skip = xa.lo & ((1ull << h) - 1);
+  const RangeX pfx{(xa.lo >> h) | (xa.hi << (64 - h)), xa.hi >> h};
+  const uint64_t nroots = ((skip + n - 1) >> h) + 1;
+  uint32_t* ctrs = (uint32_t*)(w->d_ws + 2 * buf_bytes);
+  uint4* cur = (uint4*)w->d_ws;
+  uint4* nxt = (uint4*)(w->d_ws + buf_bytes);
+  HIP_TRY(hipMemsetAsync(ctrs, 0, 16 * sizeof(uint32_t), st));
+  const uint64_t total = keys * nroots;
+  hipLaunchKernelGGL(k_rangemk_roots16<false>, dim3((unsigned)std::min<uint64_t>(cus, (total + 31) / 32)),
+                     dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, s0, (uint64_t)K, (uint32_t)party,
+                     pfx, nlev - h, range_div_make((uint32_t)nroots), (uint32_t)total, cur, blocks);
+  HIP_TRY(hipGetLastError());
+  for (uint32_t k = 0; k < m; ++k) {  // level 8N - h + k: nroots << k parents per key
+    const uint64_t parents = total << k;
+    hipLaunchKernelGGL(k_rangemk_level16, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
+                       p->rk[0], cws, cwv, cwt, (uint64_t)K, nlev - h + k, range_div_make((uint32_t)(nroots << k)),
+                       (uint32_t)parents, (const uint4*)cur, nxt, ctrs + k, blocks);
+    HIP_TRY(hipGetLastError());
+    std::swap(cur, nxt);
+  }
+  const uint64_t nnodes = total << m;
+  hipLaunchKernelGGL(k_rangemk_tail16<(int)kRangeTail>, dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock), 0, st,
+                     p->d_tab, p->rk[0], cws, cwv, cwt, np1, (uint64_t)K, nlev - kRangeTail,
+                     range_div_make((uint32_t)(nroots << m)), (uint32_t)nnodes, (const uint4*)cur, (uint32_t)skip,
+                     (uint32_t)n, (uint4*)ys, ctrs + 15, blocks);
+  HIP_TRY(hipGetLastError());
+  return DCF_OK;
+}
+
+// The slow path (MMO PRG, lambda >= 32, N > 16): key by key, each gathered into the single-key
+// layout in a buffer of the call's own and run through the single-key range path.
+static int rangemk_fallback(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb,
+                            const uint8_t* s0s, const RangeArg& A, uint64_t count, uint8_t* ys) {
+  const size_t lam = p->lambda;
+  const size_t kb = align256(dcf_cwb_bytes(nb, lam, 1));
+  DevBuf key;  // range_launch's eval owns the workspace
+  HIP_TRY(key.alloc(kb + lam));
+  uint8_t* dk = (uint8_t*)key.p;
+  HIP_TRY(hipMemsetAsync(dk, 0, kb + lam, L.st));
+  const uint8_t* np1 = cwb + dcf_cwb_np1_offset(nb, lam, K);
+  const uint32_t h = range_levels(nb, count);
+  for (uint64_t k = 0; k < K; ++k) {
+    hipLaunchKernelGGL(k_rangemk_gather, dim3(8), dim3(256), 0, L.st, cwb, np1, s0s, (uint64_t)K, k,
+                       (uint32_t)(8 * nb), (uint32_t)lam, (uint32_t)dcf_cwb_np1_offset(nb, lam, 1), dk, dk + kb);
+    HIP_TRY(hipGetLastError());
+    if (int rc = range_launch(p, L, nb, party, dk, dk + kb, A, 0, count, h, ys + k * count * lam, k == 0)) return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(L.st));  // `key` is freed on return
+  return DCF_OK;
+}
+
+int dcf_eval_range_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, int party, const uint8_t* cwb,
+                                   const uint8_t* s0s, const uint8_t* x0, uint64_t count, uint8_t* ys, void* stream) {
+  if (!p) return fail(DCF_ERR_ARG, "null prg");
+  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
+  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
+  if (!cwb || !s0s || !x0) return fail(DCF_ERR_ARG, "null argument");
+  if (n_bytes > 16 + kRangeTopMax) return fail(DCF_ERR_UNSUPPORTED, "range eval: N <= 256");
+  if (num_keys == 0 || count == 0) return DCF_OK;
+  if (!ys) return fail(DCF_ERR_ARG, "null buffer");
+  RangeArg A;
+  if (int rc = range_parse(n_bytes, x0, count, &A)) return rc;
+  DeviceGuard dg(p->device);
+  Lease L(p);
+  if (int rc = L.order((hipStream_t)stream)) return rc;
+  if (p->kind != 0 || p->lambda != 16 || n_bytes > 16)
+    return rangemk_fallback(p, L, n_bytes, num_keys, party, cwb, s0s, A, count, ys);
+  Workspace* w = L.w;
+  if (int rc = ensure_ctr(w)) return rc;
+  const uint32_t h = rangemk_levels(n_bytes, num_keys, count);
+  const uint64_t per = std::min<uint64_t>(num_keys, rangemk_keys_per_launch(h, count));
+  const uint64_t n1 = std::min<uint64_t>(count, kRangeLaunch);  // outputs of one key in a launch
+  // two ping-pong buffers of rows (32 B) up to level 8N - kRangeTail, then the work counters
+  const size_t buf_bytes = h ? align256((per * ((n1 >> h) + 2) * 32) << (h - kRangeTail)) : 0;
+  if (h)
+    if (int rc = ensure_ws(w, 2 * buf_bytes + 16 * sizeof(uint32_t), L.st)) return rc;
+  HIP_TRY(hipMemsetAsync(w->d_ctr, 0, kCtrBytes, L.st));
+  w->last_prefix = 0;
+  phase_mark(p, L, 0);
+  phase_mark(p, L, 1);
+  if ((count >> h) + 2 <= (kRangeLaunch >> h)) {  // groups of whole keys
+    for (uint64_t k0 = 0; k0 < num_keys; k0 += per) {
+      const uint64_t keys = std::min<uint64_t>(per, num_keys - k0);
+      if (int rc = rangemk_group(p, L, n_bytes, num_keys, party, cwb, s0s, k0, keys, A.x, count, h, buf_bytes,
+                                 ys + k0 * count * 16))
+        return rc;
+    }
+  } else {  // one key alone exceeds a launch: the keys one after another, 2^28 outputs at a time
+    for (uint64_t k = 0; k < num_keys; ++k)
+      for (uint64_t o = 0; o < count; o += kRangeLaunch) {
+        const uint64_t n = std::min<uint64_t>(kRangeLaunch, count - o);
+        if (int rc = rangemk_group(p, L, n_bytes, num_keys, party, cwb, s0s, k, 1, range_add(A.x, o), n, h, buf_bytes,
+                                   ys + (k * count + o) * 16))
+          return rc;
+      }
+  }
+  phase_mark(p, L, 2);
+  p->last_ws.store(w);
+  return DCF_OK;
 }
 
 int dcf_gen(dcf_prg* p, size_t n_bytes, const uint8_t* alpha, const uint8_t* beta, const uint8_t* s0_0,

@@ -424,6 +424,35 @@ class DcfImpl:
                                                 _stream(dev)))
         return ys
 
+    def range_multikey_subtree_levels(self, num_keys: int, count: int) -> int:
+        """Height h of the aligned blocks the tree path of eval_range_multikey_device expands
+        (dcf_eval_range_multikey_subtree_levels; the rule is in include/dcf_hip.h)."""
+        return int(_lib.load().dcf_eval_range_multikey_subtree_levels(self.n_bytes, int(num_keys), int(count)))
+
+    def range_keys_per_launch(self, num_keys: int, count: int) -> int:
+        """Whole keys per launch group of eval_range_multikey_device (dcf_eval_range_keys_per_launch)."""
+        return int(_lib.load().dcf_eval_range_keys_per_launch(self.n_bytes, int(num_keys), int(count)))
+
+    def eval_range_multikey_device(self, b: bool, cwb, s0s, x0, count: int, ys=None):
+        """K keys over one range: `Dcf::eval` of key k at x0 + i for i in [0, count), as a
+        (K, count, LAMBDA) device tensor.  cwb: the K-key block of gen_batch_device, s0s (K, LAMBDA).
+        Hirose LAMBDA = 16, N <= 16: one tree expansion over all keys, 2 AES blocks per output."""
+        import torch
+        lam, nb, dev = self.lam, self.n_bytes, self.prg.device
+        xb = self._x0(x0)
+        count = int(count)
+        if count < 0:
+            raise DcfError(-1, "count must not be negative")
+        K = s0s.shape[0] if s0s.dim() == 2 else -1
+        ps = _dev(s0s, "s0s", dev, shape=(K, lam))
+        pk = _dev(cwb, "cwb", dev, numel=cwb_bytes(nb, lam, K))
+        if ys is None:
+            ys = torch.empty((K, count, lam), dtype=torch.uint8, device=s0s.device)
+        py = _dev(ys, "ys", dev, numel=K * count * lam)
+        check(_lib.load().dcf_eval_range_multikey_device(self.prg.handle, nb, K, int(bool(b)), pk, ps, _ptr(xb), count,
+                                                         py, _stream(dev)))
+        return ys
+
     def eval_range(self, b: bool, k: Share, x0, count: int, ys=None):
         """Host buffers (dcf_eval_range): ys is a (count, LAMBDA) uint8 numpy array, overwritten in
         place when given.  Returns ys."""

@@ -241,6 +241,25 @@ class DcfImpl final : public Dcf<N, LAMBDA> {
   // Height of the aligned blocks eval_range expands for `count` points.
   static int range_subtree_levels(uint64_t count) { return dcf_eval_range_subtree_levels(N, count); }
 
+  // num_keys keys over one range, device form (dcf_eval_range_multikey_device): row k * count + i
+  // of ys is Dcf::eval(b, key k, x0 + i).  cwb: the K-key CWB of dcf_gen_batch_device, s0s:
+  // num_keys * LAMBDA bytes, ys: num_keys * count * LAMBDA bytes, all on the prg's device;
+  // asynchronous on `stream`, x0 is read before the call returns.
+  void eval_range_multikey_device(bool b, size_t num_keys, const uint8_t* cwb, const uint8_t* s0s,
+                                  const std::array<uint8_t, N>& x0, uint64_t count, uint8_t* ys,
+                                  void* stream = nullptr) const {
+    check(dcf_eval_range_multikey_device(prg_.handle(), N, num_keys, b ? 1 : 0, cwb, s0s, x0.data(), count, ys,
+                                         stream));
+  }
+
+  // Block height and whole keys per launch group of eval_range_multikey_device.
+  static int range_multikey_subtree_levels(size_t num_keys, uint64_t count) {
+    return dcf_eval_range_multikey_subtree_levels(N, num_keys, count);
+  }
+  static size_t range_keys_per_launch(size_t num_keys, uint64_t count) {
+    return dcf_eval_range_keys_per_launch(N, num_keys, count);
+  }
+
  private:
   const PrgT& prg_;
 };

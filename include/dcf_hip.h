@@ -335,6 +335,51 @@ int dcf_eval_range(dcf_prg* prg, size_t n_bytes, int party, const uint8_t* cwb, 
  * clipped edge blocks at most 4 * 2^h blocks in all. */
 int dcf_eval_range_subtree_levels(size_t n_bytes, uint64_t count);
 
+/* Multi-key contiguous-range eval: K keys over one range, ys[(k * count + i) * lambda ..] =
+ * Dcf::eval(party, key k, x0 + i) — dcf_eval_range_device of every key of a K-key block in one
+ * call (lookup-table / spline protocols, batched comparison gates: many keys over one small
+ * domain or window).  cwb is the K-key correction-word block as dcf_gen_batch_device writes it and
+ * dcf_eval_multikey_device reads it ([n][K][lambda], [n][K][lambda], [n][K], cw_np1[K][lambda] at
+ * dcf_cwb_np1_offset(n_bytes, lambda, K)); s0s: K * lambda bytes; ys: K * count * lambda bytes;
+ * all device pointers.  x0 is a HOST pointer to n_bytes big-endian bytes, read before the call
+ * returns.  Asynchronous on `stream`.
+ *   Hirose PRG, lambda = 16, N <= 16: every key's range is covered by the same
+ *   nroots = (((x0 mod 2^h) + count - 1) >> h) + 1 aligned blocks of 2^h leaves
+ *   (h = dcf_eval_range_multikey_subtree_levels).  The K * nroots roots are walked from their keys'
+ *   seeds, the levels below are expanded breadth-first over all keys at once (one launch per
+ *   level, the keys one after another in every node buffer, each in leaf order) and the last 4
+ *   levels depth-first in registers: 2 AES blocks per output plus 2 (8N - h) per root.  Correction
+ *   words are read per lane at [level][key].  Node and output indices are 32-bit within a launch
+ *   group of dcf_eval_range_keys_per_launch whole keys (keys * (nroots << h) <= 2^28; only the key
+ *   offset is 64-bit across groups); when one key alone exceeds 2^28 outputs the keys run one after
+ *   another, 2^28 outputs per group.  The workspace holds two buffers of the nodes four levels
+ *   above the leaves of a group (at most 2 x 512 MiB).  dcf_prg_last_eval_blocks then reports the
+ *   AES blocks of the root paths, the interior levels and the tail, clipped leaves included, summed
+ *   over all keys and groups.
+ *   Otherwise (MMO PRG, lambda >= 32, N > 16) — the slow path: key by key, each gathered into the
+ *   single-key layout and run through dcf_eval_range_device's path; it waits for the stream.
+ * Errors, nothing launched: null prg / cwb / s0s / x0, null ys with work to do, bad party ->
+ * DCF_ERR_ARG; n_bytes == 0 -> DCF_ERR_N; N > 256 -> DCF_ERR_UNSUPPORTED; x0 + count > 2^(8N) ->
+ * DCF_ERR_ARG.  num_keys == 0 or count == 0 -> DCF_OK, nothing written. */
+int dcf_eval_range_multikey_device(dcf_prg* prg, size_t n_bytes, size_t num_keys, int party, const uint8_t* cwb,
+                                   const uint8_t* s0s, const uint8_t* x0, uint64_t count, uint8_t* ys, void* stream);
+
+/* Height h of the aligned blocks the tree path of dcf_eval_range_multikey_device uses (pure
+ * arithmetic, no device access; 0 for n_bytes == 0 or num_keys == 0):
+ *   count < 64 or num_keys * count < 2^12:  h = 0 — every point is walked on its own;
+ *   otherwise:                              h = min(8N, 14, floor(log2(count)) - 2).
+ * So h = 0 or 4 <= h <= min(8N, 14), and 2^h <= count / 4: a key has at least 4 blocks and its two
+ * clipped edge blocks waste at most count / 2 leaves.  The parallelism comes from K * nroots, so
+ * the blocks are as tall as that allows (root paths cost 2 (8N - h) blocks per 2^h leaves); below
+ * 2^12 outputs in the whole call the direct walk's single launch wins.  It is not the single-key
+ * rule at num_keys = 1. */
+int dcf_eval_range_multikey_subtree_levels(size_t n_bytes, size_t num_keys, uint64_t count);
+
+/* Whole keys per launch group of that path: the most keys with keys * (((count >> h) + 2) << h) <=
+ * 2^28 (every key has at most (count >> h) + 2 blocks), at least 1; num_keys enters through h
+ * only.  1 also when one key alone exceeds a launch. */
+size_t dcf_eval_range_keys_per_launch(size_t n_bytes, size_t num_keys, uint64_t count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@
 pub mod ffi;
 
 use std::ffi::CStr;
-use std::os::raw::c_int;
+use std::os::raw::{c_int, c_void};
 
 use dcf::{BoundState, CmpFn, Cw, Dcf, Share};
 
@@ -153,6 +153,31 @@ impl<const N: usize, const LAMBDA: usize> DcfHip<N, LAMBDA> {
     /// Height of the aligned blocks `eval_range` expands for `count` points (`dcf_eval_range_subtree_levels`).
     pub fn range_subtree_levels(count: u64) -> i32 {
         unsafe { ffi::dcf_eval_range_subtree_levels(N, count) }
+    }
+
+    /// `num_keys` keys over one range, device buffers (`dcf_eval_range_multikey_device`): row
+    /// `k * count + i` of `ys` is `Dcf::eval(b, key k, x0 + i)`.  `cwb` is the K-key block of
+    /// `dcf_gen_batch_device`, `s0s` `num_keys * LAMBDA` bytes, `ys` `num_keys * count * LAMBDA`
+    /// bytes; asynchronous on `stream`, `x0` is read before the call returns.
+    ///
+    /// # Safety
+    /// `cwb`, `s0s` and `ys` must be device buffers of those sizes on the prg's device, valid until
+    /// `stream` has run the call.
+    pub unsafe fn eval_range_multikey_device(&self, b: bool, num_keys: usize, cwb: *const u8, s0s: *const u8,
+                                             x0: &[u8; N], count: u64, ys: *mut u8, stream: *mut c_void)
+                                             -> Result<(), DcfHipError> {
+        check(ffi::dcf_eval_range_multikey_device(self.prg, N, num_keys, b as c_int, cwb, s0s, x0.as_ptr(), count, ys,
+                                                  stream))
+    }
+
+    /// Height of the aligned blocks `eval_range_multikey_device` expands (`dcf_eval_range_multikey_subtree_levels`).
+    pub fn range_multikey_subtree_levels(num_keys: usize, count: u64) -> i32 {
+        unsafe { ffi::dcf_eval_range_multikey_subtree_levels(N, num_keys, count) }
+    }
+
+    /// Whole keys per launch group of `eval_range_multikey_device` (`dcf_eval_range_keys_per_launch`).
+    pub fn range_keys_per_launch(num_keys: usize, count: u64) -> usize {
+        unsafe { ffi::dcf_eval_range_keys_per_launch(N, num_keys, count) }
     }
 }
 

@@ -20,6 +20,8 @@
 #   pmc     W "COUNTERS" [bench args]    one extra PMC pass (mean per dispatch per kernel printed)
 #   range   [range_bench args]      scripts/range_bench.py: range eval vs eval_device on the same points and
 #                                   vs full-domain eval at N = 4 -> range_bench.json (copy to profiles/)
+#   rangemk [range_multikey_bench args]  scripts/range_multikey_bench.py: K keys over one range vs a loop of
+#                                   single-key range calls and vs multi-key point eval -> range_multikey_bench.json
 set -o pipefail
 export TMPDIR=/tmp
 TAG=$1; CMD=$2; shift 2
@@ -154,6 +156,21 @@ if f:
     print("N=4 whole domain: range %.4g out/s, full-domain %.4g out/s (%.3f-%.3f ms), range/full %.3f, inside spread %s" % (
         f["range_outputs_per_s"], f["full_domain_outputs_per_s"], f["full_domain"]["min_ms"], f["full_domain"]["max_ms"],
         f["range_over_full_domain_ms"], f["range_inside_full_domain_spread"]))
+PY
+  ;;
+rangemk)  # multi-key range eval vs a loop of single-key range calls and vs multi-key point eval
+  timeout -k 10 900 python scripts/range_multikey_bench.py --out $O/range_multikey_bench.json "$@" \
+    > $O/range_multikey_bench.log 2> $O/range_multikey_bench.err || { tail -20 $O/range_multikey_bench.err; exit 1; }
+  python - $O/range_multikey_bench.json <<'PY'
+import json, sys
+d = json.load(open(sys.argv[1]))
+for r in d["shapes"]:
+    print("rangemk N=%d K=2^%d count=2^%d h=%d %.4g out/s (%.3f-%.3f ms) %.3f blocks/out lds=%.3f loop %.1fx (beyond spread %s) "
+          "pointwise %.1fx equal=%s/%s" % (
+              r["n_bytes"], r["num_keys"].bit_length() - 1, r["count"].bit_length() - 1, r["subtree_levels"],
+              r["outputs_per_s"], r["multikey"]["min_ms"], r["multikey"]["max_ms"], r["blocks_per_output"],
+              r["lds_bound_frac"], r["speedup_vs_loop"], r["faster_than_loop_beyond_spread"], r["speedup_vs_pointwise"],
+              r["loop_outputs_equal"], r["pointwise_outputs_equal"]))
 PY
   ;;
 *)

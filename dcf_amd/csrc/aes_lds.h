@@ -153,6 +153,19 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
   return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 }
 
+// One v_bitop3_b32 with its truth table written as the expression itself over the three operand
+// patterns: bop3<kTa ^ (kTb & kTc)>(a, b, c) = a ^ (b & c).
+constexpr uint32_t kTa = 0xF0u, kTb = 0xCCu, kTc = 0xAAu;
+template <uint32_t TT>
+__device__ __forceinline__ uint32_t bop3(uint32_t a, uint32_t b, uint32_t c) {
+  return __builtin_amdgcn_bitop3_b32(a, b, c, TT & 0xFFu);
+}
+constexpr uint32_t kTtXorAnd = kTa ^ (kTb & kTc);              // a ^ (b & c)
+constexpr uint32_t kTtXorAndNot = kTa ^ (kTb & ~kTc);          // a ^ (b & ~c)
+constexpr uint32_t kTtSel = (kTa & ~kTc) | (kTb & kTc);        // c ? b : a
+constexpr uint32_t kTtAndOr = kTa & (kTb | kTc);               // a & (b | c)
+constexpr uint32_t kTtAndNotNot = kTa & ~kTb & ~kTc;           // a & ~b & ~c
+
 // NB independent AES-256 encryptions under one key schedule (FIPS-197),
 // interleaved for ILP.  st holds LE column words.
 template <int NB>

@@ -275,9 +275,32 @@ __global__ __launch_bounds__(kKmThreads) void k_cw_keymajor(const uint4* __restr
   }
 }
 
-// B reuse over whole runs of right steps at t = 0 (A/B knob, see the reuse block in stream_run).
-#ifndef DCF_REUSE_RUN
-#define DCF_REUSE_RUN 0
+// B reuse over whole runs of right steps at t = 0 (A/B knob, see the reuse section in stream_run).
+// Per instance family, x words in registers: single key with N > 4 or runtime width (C1 / C3),
+// single key with x in one word (C2), multi-key (C5); and the instances that load x per word
+// (N no multiple of 4, or N > 16), single- and multi-key.  -DDCF_REUSE_RUN=v sets all four.
+// On everywhere since the update went to mask form (r07a, same box, 3 alternating runs, ms per
+// step, parent / knob off / knob on): C3 475.5-477.5 / 467.1-467.6 / 449.2-449.5, C2 3.279-3.308 /
+// 3.211-3.251 / 3.130-3.177, C5 316.0-316.3 / 310.0-310.6 / 299.1-299.7; before it (r05am) the
+// run chain's ~45 VALU per iteration ate the gain.  The x-per-word instances were not timed: with
+// the knob off three of them spill 6-8 VGPRs at 128, with it on none does.
+#ifdef DCF_REUSE_RUN
+#define DCF_REUSE_RUN_SK DCF_REUSE_RUN
+#define DCF_REUSE_RUN_SK4 DCF_REUSE_RUN
+#define DCF_REUSE_RUN_MK DCF_REUSE_RUN
+#define DCF_REUSE_RUN_XW DCF_REUSE_RUN
+#endif
+#ifndef DCF_REUSE_RUN_XW
+#define DCF_REUSE_RUN_XW 1
+#endif
+#ifndef DCF_REUSE_RUN_SK
+#define DCF_REUSE_RUN_SK 1
+#endif
+#ifndef DCF_REUSE_RUN_SK4
+#define DCF_REUSE_RUN_SK4 1
+#endif
+#ifndef DCF_REUSE_RUN_MK
+#define DCF_REUSE_RUN_MK 1
 #endif
 // STG (staged rows; single key, prefix table, x in one word — C2): a wave claims its points in
 // halves of kStgUnit (from its own 256-point counter claims: 32-point atomics on the one counter ran
@@ -334,6 +357,7 @@ __device__ __forceinline__ void stream_run(
   static_assert(!STG || (!MULTI && XREG && PFX && NBC > 0 && NBC <= 4),
                 "staged rows: single key, prefix table, x in one word");
   const uint32_t nbytes = NBC ? (uint32_t)NBC : nbytes_rt;
+  constexpr bool RUN = !XREG ? DCF_REUSE_RUN_XW : MULTI ? DCF_REUSE_RUN_MK : (NBC && NBC <= 4) ? DCF_REUSE_RUN_SK4 : DCF_REUSE_RUN_SK;
   const uint32_t lc = lane_const();
   const uint32_t nlev = 8u * nbytes;
   // one launch covers < 2^32 points (the host cuts larger batches): 32-bit work distribution
@@ -494,39 +518,45 @@ __device__ __forceinline__ void stream_run(
     if (!__ballot(any) && !pend) break;
     // Correction words of each stream's current level (vector loads, issued before the AES),
     // and of the next level for a stream whose step may end with B still valid (a right
-    // step at t = 0 keeps s: see "B reuse" below).
+    // step at t = 0 keeps s: see "B reuse" below).  The next level's are loaded unconditionally
+    // (L1-resident): loads under a divergent branch made the compiler wait for them before the AES.
     uint4 cs[NS], cv[NS], cs2[NS], cv2[NS];
     uint32_t ct[NS], ct2[NS];
-    bool maybe[NS];  // the next level's CWs were loaded
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
-      // CW row: the key-major digest row (MULTI: cw_s = digest, 2 uint4 per level, cw_t = its t
-      // bytes); for one key the row is the level itself (a 32-bit index: ci only mirrors lev
-      // there, and a retired stream's lev is reset to 0)
-      const uint32_t cwi = MULTI ? L.ci[i] : L.lev[i];
       if (MULTI) {
+        // Key-major digest row ci (cw_s = digest, 2 uint4 per level, cw_t = its t bytes).  One
+        // launch's digest spans up to 2^30 rows x 32 B, past a 32-bit byte offset, so the rows
+        // keep 64-bit indexing, and the clamp at the key's last level stays: the row after the
+        // last key's last level would be the first 32 B of dig_t, which holds only K * 8N bytes
+        // (16 for K = 2, N = 1), and dig_t[K * 8N] is the first byte past the allocation.
+        const uint32_t cwi = L.ci[i];
+        const uint32_t c2 = cwi + (L.lev[i] + 1u < nlev ? 1u : 0u);
         cs[i] = cw_s[2 * cwi];
         cv[i] = cw_s[2 * cwi + 1];
-      } else {
-        cs[i] = cw_s[cwi];
-        cv[i] = cw_v[cwi];
-      }
-      ct[i] = cw_t[cwi];
-      // XREG: a fresh stream's x word is still in the queue; its first step is a B step
-      // at the root, whose seed may be unmasked, so no reuse follows it anyway.
-      maybe[i] = L.alive[i] && L.ph[i] == 0u && L.t[i] == 0u && (!XREG || PFX || !L.fresh[i]) &&
-                 (L.cur[i] >> 31) != 0u && L.lev[i] + 1u < nlev;
-      // Loaded unconditionally (L1-resident): loads under a divergent branch made the
-      // compiler wait for them before the AES.
-      const uint32_t c2 = cwi + (L.lev[i] + 1u < nlev ? 1u : 0u);
-      if (MULTI) {
+        ct[i] = cw_t[cwi];
         cs2[i] = cw_s[2 * c2];
         cv2[i] = cw_s[2 * c2 + 1];
+        ct2[i] = cw_t[c2];
       } else {
-        cs2[i] = cw_s[c2];
-        cv2[i] = cw_v[c2];
+        // One key: the row is the level (a retired stream's lev is reset to 0), addressed as a
+        // uniform base plus a 32-bit byte offset, the next level's at the immediate +16 / +1.
+        // No clamp at the last level lev = 8N - 1: its next-level words are never used (k and lm
+        // below are 0 at nl = 8N) and lie inside the key's CWB (include/dcf_hip.h: cw_s[8N][16],
+        // cw_v[8N][16], cw_t[8N], zero padding to 16, cw_np1[16]): cw_s[8N] is cw_v[0]; cw_v[8N] is
+        // the 16 B at cw_t, i.e. cw_t[0..8N) (8N >= 8) and, for N = 1, its 8 B of padding; cw_t[8N]
+        // is the first padding byte or, where 8N is a multiple of 16, cw_np1[0].
+        const uint32_t off = L.lev[i] << 4;
+        const uint8_t* ps = reinterpret_cast<const uint8_t*>(cw_s) + off;
+        const uint8_t* pv = reinterpret_cast<const uint8_t*>(cw_v) + off;
+        const uint8_t* pt = cw_t + L.lev[i];
+        cs[i] = *reinterpret_cast<const uint4*>(ps);
+        cv[i] = *reinterpret_cast<const uint4*>(pv);
+        ct[i] = pt[0];
+        cs2[i] = *reinterpret_cast<const uint4*>(ps + 16);
+        cv2[i] = *reinterpret_cast<const uint4*>(pv + 16);
+        ct2[i] = pt[1];
       }
-      ct2[i] = cw_t[c2];
     }
     // Slot i encrypts ~s (B) in phase 0 and s (A) in phase 1.
     uint32_t st[NS][4];
@@ -566,92 +596,101 @@ __device__ __forceinline__ void stream_run(
                    "+v"(cv2[i].y), "+v"(cv2[i].z), "+v"(cv2[i].w), "+v"(ct2[i]));
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
+      // The level update in mask form: every per-stream condition is a 0 / ~0 word formed once,
+      // and each word of s and v takes only three-input ops (bop3, aes_lds.h) with those masks;
+      // kMaskLast is folded into word 3's masks, so words 0-2 pay nothing for it.
+      uint32_t fm = 0u;  // the stream's first step: its x word is still in the queue
       if (XREG && !PFX) {  // next 32 x bits from the word queue (raw loads, byte-swapped here)
         const bool nw = L.fresh[i];
+        fm = nw ? ~0u : 0u;
         L.cur[i] = nw ? bswap32(L.xw[i][0]) : L.cur[i];
         L.xw[i][0] = nw ? L.xw[i][1] : L.xw[i][0];
         L.xw[i][1] = nw ? L.xw[i][2] : L.xw[i][1];
         L.xw[i][2] = nw ? L.xw[i][3] : L.xw[i][2];
         L.fresh[i] = false;
       }
-      const uint32_t p = L.ph[i], xb = L.cur[i] >> 31;  // Msb0 bit of x (lib.rs:181)
-      const uint32_t adv = L.alive[i] ? (p | xb) : 0u;   // this step finishes the level
-      const uint32_t inv = p - 1u;                        // all ones on a B step
-      const uint32_t keepB = xb - 1u;                     // all ones when going left
-      const uint32_t tm = 0u - L.t[i], am = 0u - adv, pm = 0u - p;
+      const uint32_t pm = 0u - L.ph[i];                            // all ones on an A step
+      const uint32_t xm = (uint32_t)((int32_t)L.cur[i] >> 31);     // all ones going right: Msb0 bit of x (lib.rs:181)
+      const uint32_t tm = 0u - L.t[i];
+      const uint32_t am = bop3<kTtAndOr>(L.alive[i] ? ~0u : 0u, pm, xm);  // this step finishes the level
+      const uint32_t adv = am & 1u;
+      const uint32_t inv = ~pm;                                    // all ones on a B step
+      const uint32_t ik = ~(pm | xm);                              // B step going left
+      const uint32_t itm = tm & ~pm, apm = am & pm, atm = am & tm;
+      const uint32_t ikw[4] = {ik, ik, ik, ik & kMaskLast};
+      const uint32_t invw[4] = {inv, inv, inv, inv & kMaskLast};
+      const uint32_t apmw[4] = {apm, apm, apm, apm & kMaskLast};
       const uint32_t csw[4] = {cs[i].x, cs[i].y, cs[i].z, cs[i].w};
       const uint32_t cvw[4] = {cv[i].x, cv[i].y, cv[i].z, cv[i].w};
-      uint32_t d[4];  // (A^s) or (B^~s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) d[j] = st[i][j] ^ L.s[i][j] ^ inv;
-      const uint32_t d0 = d[0];
       // B reuse: a right step at t = 0 leaves s = s & M, which is s itself when s is
       // already masked (every seed below the root: side & M ^ t*cw.s, cw.s masked), so
       // the next level's PRG(s) is this one's and its B is d ^ ~s, already in hand.
-      const bool reuse = maybe[i] && (L.s[i][3] & ~kMaskLast) == 0u;
+      // rm: this is such a step (alive, B step, right, t = 0, s masked, not the stream's first
+      // step: that is a B step at the root, whose seed may be unmasked).
+      const uint32_t s3bad = (uint32_t)__builtin_amdgcn_sbfe((int)L.s[i][3], 24u, 1u);  // all ones: bit ~M of s set
+      const uint32_t rm = bop3<kTtAndNotNot>(bop3<kTtAndNotNot>(am, pm, tm), s3bad, fm);
+      uint32_t d[4];  // (A^s) or (B^~s)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) d[j] = xor3(st[i][j], L.s[i][j], inv);
+      const uint32_t d0 = d[0];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const uint32_t msk = (j == 3) ? kMaskLast : 0xFFFFFFFFu;
-        const uint32_t in = L.s[i][j] ^ inv;
         // B step: v ^= v_hat(side) ^ t*cw.v, v_hat = (~s ^ [left] B) & M   (lib.rs:182/186)
-        const uint32_t vhat = (in ^ (st[i][j] & keepB)) & msk;
-        L.v[i][j] ^= inv & (vhat ^ (tm & cvw[j]));
+        //   = [B step, left] B & M  ^  [B step] ~s & M  ^  [B step, t] cw.v
+        uint32_t vj = bop3<kTtXorAnd>(L.v[i][j], st[i][j], ikw[j]);
+        vj = bop3<kTtXorAndNot>(vj, invw[j], L.s[i][j]);
+        L.v[i][j] = bop3<kTtXorAnd>(vj, cvw[j], itm);
         // level done: s' = s(side) ^ t*cw.s, s(side) = (A^s)&M (left) or s&M (right)  (lib.rs:177-178)
-        const uint32_t sx = L.s[i][j] ^ (st[i][j] & pm);  // p: A ^ s
-        const uint32_t sn = (sx & msk) ^ (tm & csw[j]);
-        L.s[i][j] = (am & sn) | (~am & L.s[i][j]);
+        //   = s & M  ^  [done, A step] A & M  ^  [done, t] cw.s
+        uint32_t sj = L.s[i][j];
+        if (j == 3) sj &= ~am | kMaskLast;
+        sj = bop3<kTtXorAnd>(sj, st[i][j], apmw[j]);
+        L.s[i][j] = bop3<kTtXorAnd>(sj, csw[j], atm);
       }
-      // t' = lsb(side) ^ t & cw.t(side)   (lib.rs:179-180, 183/187)
-      const uint32_t tb = (d0 ^ (L.t[i] & (ct[i] >> xb))) & 1u;
-      L.t[i] = (am & tb) | (~am & L.t[i]);
-      L.ph[i] = adv ^ 1u;
+      // t' = lsb(side) ^ t & cw.t(side)   (lib.rs:179-180, 183/187); ct >> 1 going right
+      const uint32_t tb = bop3<kTtXorAnd>(d0, L.t[i], ct[i] >> (xm & 1u));
+      L.t[i] = bop3<kTtSel>(L.t[i], tb, adv);
       uint32_t nl = L.lev[i] + adv;
       L.cur[i] <<= adv;
       // (x in one word, NBC <= 4: the only crossing ends the point, so no next word is taken)
       if (!(NBC && NBC <= 4) && adv && (nl & 31u) == 0u) stream_next_word<NS, XREG, MULTI>(L, i, nl, nlev, nbytes);
-      L.ci[i] += adv;
-      {  // reuse: level nl with B known: its B half now, without an AES slot (branch-free)
-        const uint32_t xb2 = L.cur[i] >> 31, t1 = L.t[i], tm1 = 0u - t1;
-        const uint32_t rm = 0u - (uint32_t)reuse, rr = rm & (0u - xb2);  // reuse / reuse and right
-        const uint32_t cs2w[4] = {cs2[i].x, cs2[i].y, cs2[i].z, cs2[i].w};
-        const uint32_t cv2w[4] = {cv2[i].x, cv2[i].y, cv2[i].z, cv2[i].w};
+      // Reuse (rm): B of level nl is known, so its B half is taken now, without an AES slot.
+      //   t = 1: one step.  Right: v ^= ~s & M ^ cw.v, s ^= cw.s, t' = lsb(B^~s) ^ cw.tr, the level
+      //     ends (lib.rs:178-186).  Left: v ^= (B^~s) & M ^ cw.v, and A is the next slot.
+      //   t = 0: no CW enters, a right step keeps s and t, and so the next level has the same B
+      //     again.  RUN: a whole run of k right steps is taken (v ^= ~s & M for odd k), up to the x
+      //     word's end (the next word's first step recomputes B) and level 8N; without RUN k <= 1.
+      //     The left step that ends the run inside the x word (RUN; without RUN only at k = 0) has
+      //     its B half too, leaving A for the next slot.
+      const uint32_t t1 = L.t[i], tm1 = 0u - t1;
+      const uint32_t ones = RUN ? (uint32_t)__clz((int)~L.cur[i]) : L.cur[i] >> 31;  // leading 1 bits of x
+      const uint32_t klim = RUN ? (bop3<kTa & (kTb ^ kTc)>(rm, tm1, 32u) & 33u) : (rm & 1u);  // rm ? (t ? 1 : 32) : 0
+      const uint32_t k = min(min(ones, nlev - nl), klim);
+      const uint32_t ko = (uint32_t)__builtin_amdgcn_sbfe((int)k, 0u, 1u);  // k odd
+      nl += k;
+      L.cur[i] <<= k;
+      const bool cross = k != 0u && (nl & 31u) == 0u;  // the right steps used up the x word
+      // the left step after the right steps: below level 8N, x bit 0, s still the one B was made from
+      const uint32_t below = (uint32_t)((int32_t)(nl - nlev) >> 31);
+      const uint32_t xm2 = (uint32_t)((int32_t)L.cur[i] >> 31);
+      const uint32_t lm0 = bop3<kTtAndNotNot>(rm & below, xm2, RUN ? (tm1 & ko) : ko);
+      const uint32_t lm = cross ? 0u : lm0;
+      const uint32_t vm2 = bop3<kTtAndOr>(tm1, ko, lm), sm = tm1 & ko;  // cw.v / cw.s of level nl enter
+      const uint32_t kow[4] = {ko, ko, ko, ko & kMaskLast};
+      const uint32_t lmw[4] = {lm, lm, lm, lm & kMaskLast};
+      const uint32_t cs2w[4] = {cs2[i].x, cs2[i].y, cs2[i].z, cs2[i].w};
+      const uint32_t cv2w[4] = {cv2[i].x, cv2[i].y, cv2[i].z, cv2[i].w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const uint32_t msk = (j == 3) ? kMaskLast : 0xFFFFFFFFu;
-          // v ^= v_hat(side) ^ t*cw.v: right ~s & M, left (B^~s) & M   (lib.rs:182/186)
-          L.v[i][j] ^= rm & ((((xb2 ? ~L.s[i][j] : d[j]) & msk) ^ (tm1 & cv2w[j])));
-          L.s[i][j] ^= rr & tm1 & cs2w[j];  // right: s' = s & M ^ t*cw.s   (lib.rs:178)
-        }
-        // right: the level ends, t' = lsb(B^~s) ^ t & cw.tr (lib.rs:180); left: A next
-        L.t[i] = rr ? ((d0 ^ (t1 & (ct2[i] >> 1))) & 1u) : L.t[i];
-        L.ph[i] = (reuse && !xb2) ? 1u : L.ph[i];
-        nl += rr & 1u;
-        L.cur[i] <<= (rr & 1u);
-        L.ci[i] += rr & 1u;
-        if (!(NBC && NBC <= 4) && rr && (nl & 31u) == 0u) stream_next_word<NS, XREG, MULTI>(L, i, nl, nlev, nbytes);
-        if (DCF_REUSE_RUN) {
-          // A reused right step that left t = 0 (t1 = 0) kept s, so the next level has the same
-          // B again: a run of k further right steps keeps s and t = 0 and XORs ~s & M into v k
-          // times (lib.rs:178-186 with t = 0: no CW enters); the left step that ends the run has
-          // its B half too (v ^= (B ^ ~s) & M), leaving A for the next slot.  The run stops at the
-          // x word's end (the next word's first step recomputes B).
-          const bool go = rr && t1 == 0u && (nl & 31u) != 0u && nl < nlev;
-          const uint32_t k = go ? min((uint32_t)__clz(~L.cur[i]), nlev - nl) : 0u;
-          const uint32_t ko = 0u - (k & 1u);
-          nl += k;
-          L.cur[i] <<= k;
-          L.ci[i] += k;
-          const uint32_t lm = 0u - (uint32_t)(go && nl < nlev && (nl & 31u) != 0u);  // the left step after the run
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const uint32_t msk = (j == 3) ? kMaskLast : 0xFFFFFFFFu;
-            L.v[i][j] ^= ((ko & ~L.s[i][j]) ^ (lm & d[j])) & msk;
-          }
-          L.ph[i] = lm ? 1u : L.ph[i];
-          if (!(NBC && NBC <= 4) && go && k && (nl & 31u) == 0u && nl < nlev)
-            stream_next_word<NS, XREG, MULTI>(L, i, nl, nlev, nbytes);
-        }
+      for (int j = 0; j < 4; ++j) {
+        uint32_t vj = bop3<kTtXorAndNot>(L.v[i][j], kow[j], L.s[i][j]);  // right, k odd: ~s & M
+        vj = bop3<kTtXorAnd>(vj, d[j], lmw[j]);                          // left: (B^~s) & M
+        L.v[i][j] = bop3<kTtXorAnd>(vj, cv2w[j], vm2);
+        L.s[i][j] = bop3<kTtXorAnd>(L.s[i][j], cs2w[j], sm);
       }
+      L.t[i] = bop3<kTtSel>(t1, d0 ^ (ct2[i] >> 1), sm & 1u);
+      L.ph[i] = bop3<kTa | (kTb & kTc)>(adv ^ 1u, lm, 1u);
+      if (!(NBC && NBC <= 4) && cross) stream_next_word<NS, XREG, MULTI>(L, i, nl, nlev, nbytes);
+      if (MULTI) L.ci[i] += adv + k;
       L.lev[i] = nl;
     }
     // Finished points: y = v ^ s_n ^ t_n*cw_np1 (lib.rs:192), then refill.  (vmcnt counts

@@ -41,7 +41,6 @@
 #include "kernels_mmo_wide.h"
 #include "kernels_wide_stream.h"
 #include "kernels_range.h"
-#include "kernels_range_mk.h"
 
 namespace {
 
@@ -293,7 +292,8 @@ uint32_t prefix_split(uint32_t levels) { return levels > 18u ? 8u : (levels > 10
 // Depth-first tail of k_prefix_build16: the last H <= kPfxDfsMax levels, once the workgroup's
 // level holds at least one node per thread (2^10 = kBlock).
 // Full-domain eval: the last kFdTail levels in registers, depth-first (k_fd_dfs16; 5 levels:
-// 128 VGPRs + scratch spills), the levels above by one k_prefix_build16 launch.
+// 128 VGPRs + scratch spills), the levels above by one k_prefix_build16 launch.  Range eval: the
+// same tail below its breadth-first levels (k_range_tail16).
 constexpr uint32_t kFdTail = 4;
 uint32_t prefix_dfs_levels(uint32_t levels, uint32_t S) {
   const uint32_t cap = kPfxDfsMax;
@@ -2092,6 +2092,16 @@ static int range_parse(size_t nb, const uint8_t* x0, uint64_t count, RangeArg* A
   return DCF_OK;
 }
 
+// What every range entry point checks first (as check_eval_args; ys may be null when there is
+// nothing to write, so the callers look at it after their counts).
+static int check_range_args(dcf_prg* p, size_t n_bytes, int party, const void* cwb, const void* s0s, const void* x0) {
+  if (!p) return fail(DCF_ERR_ARG, "null prg");
+  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
+  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
+  if (!cwb || !s0s || !x0) return fail(DCF_ERR_ARG, "null argument");
+  return DCF_OK;
+}
+
 // Points [off, off + cnt) of the range as N-byte strings at xs.
 static int range_points(const RangeArg& A, size_t nb, uint64_t off, uint64_t cnt, uint8_t* xs, hipStream_t st) {
   for (uint64_t done = 0; done < cnt;) {
@@ -2104,6 +2114,75 @@ static int range_points(const RangeArg& A, size_t nb, uint64_t off, uint64_t cnt
     HIP_TRY(hipGetLastError());
     done += n;
   }
+  return DCF_OK;
+}
+
+// Workspace of the tree path: two ping-pong buffers of *buf_bytes each — the rows (32 B) of the
+// level above the tail, for `keys` keys with n <= 2^28 outputs each in a launch group (4 B per
+// output in all) — then kRangeCtrs work counters, one per level launch and the tail's last.
+// h = 0 needs none.
+constexpr uint32_t kRangeCtrs = 16;
+static size_t range_ws_bytes(uint64_t keys, uint64_t n, uint32_t h, size_t* buf_bytes) {
+  *buf_bytes = h ? align256((keys * ((n >> h) + 2) * 32) << (h - kFdTail)) : 0;
+  return h ? 2 * *buf_bytes + kRangeCtrs * sizeof(uint32_t) : 0;
+}
+
+// One launch group of the tree path (Hirose, lambda = 16, N <= 16): keys [key0, key0 + keys) of a
+// K-key block over the n <= 2^28 points from xa, keys * n <= 2^28; the outputs of key key0 + k go
+// to rows [k * n, (k + 1) * n) of ys (several keys in a group: n is the call's count).  KP: the
+// kernels' key policy — RangeOneKey takes key0 = 0, keys = K = 1.  The caller has sized the
+// workspace (range_ws_bytes) and zeroed the block count.
+extern "C++" template <class KP>
+static int range_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb, const uint8_t* s0s,
+                       uint64_t key0, uint64_t keys, const RangeX xa, uint64_t n, uint32_t h, size_t buf_bytes,
+                       uint8_t* ys) {
+  using Idx = typename KP::Idx;
+  hipStream_t st = L.st;
+  Workspace* w = L.w;
+  const size_t lam = 16;
+  const uint32_t nlev = (uint32_t)(8 * nb);
+  const uint4* cws = (const uint4*)cwb + key0;
+  const uint4* cwv = (const uint4*)(cwb + (size_t)nlev * K * lam) + key0;
+  const uint8_t* cwt = cwb + 2 * (size_t)nlev * K * lam + key0;
+  const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(nb, lam, K)) + key0;
+  const uint4* s0 = (const uint4*)s0s + key0;
+  unsigned long long* blocks = reinterpret_cast<unsigned long long*>(w->d_ctr) + 1;
+  const uint64_t cus = (uint64_t)p->cus;
+  if (h == 0) {  // every point is its own root: the root walk writes y
+    const uint64_t total = keys * n;
+    hipLaunchKernelGGL((k_range_roots16<true, KP>), dim3((unsigned)std::min<uint64_t>(cus, (total + 31) / 32)),
+                       dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, s0, KP::make(K, (uint32_t)n),
+                       (uint32_t)party, xa, nlev, (Idx)total, (uint4*)ys, blocks);
+    HIP_TRY(hipGetLastError());
+    return DCF_OK;
+  }
+  const uint32_t m = h - kFdTail;  // breadth-first levels below a root
+  const uint64_t skip = xa.lo & ((1ull << h) - 1);
+  const RangeX pfx{(xa.lo >> h) | (xa.hi << (64 - h)), xa.hi >> h};
+  const uint64_t nroots = ((skip + n - 1) >> h) + 1;  // <= (n >> h) + 2
+  uint32_t* ctrs = (uint32_t*)(w->d_ws + 2 * buf_bytes);
+  uint4* cur = (uint4*)w->d_ws;
+  uint4* nxt = (uint4*)(w->d_ws + buf_bytes);
+  HIP_TRY(hipMemsetAsync(ctrs, 0, kRangeCtrs * sizeof(uint32_t), st));
+  const uint64_t total = keys * nroots;
+  hipLaunchKernelGGL((k_range_roots16<false, KP>), dim3((unsigned)std::min<uint64_t>(cus, (total + 31) / 32)),
+                     dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, s0, KP::make(K, (uint32_t)nroots),
+                     (uint32_t)party, pfx, nlev - h, (Idx)total, cur, blocks);
+  HIP_TRY(hipGetLastError());
+  for (uint32_t k = 0; k < m; ++k) {  // level 8N - h + k: nroots << k parents per key
+    const uint64_t parents = total << k;
+    hipLaunchKernelGGL(k_range_level16<KP>, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
+                       p->rk[0], cws, cwv, cwt, KP::make(K, (uint32_t)(nroots << k)), nlev - h + k, (uint32_t)parents,
+                       (const uint4*)cur, nxt, ctrs + k, blocks);
+    HIP_TRY(hipGetLastError());
+    std::swap(cur, nxt);
+  }
+  const uint64_t nnodes = total << m;
+  hipLaunchKernelGGL((k_range_tail16<(int)kFdTail, KP>), dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock), 0, st,
+                     p->d_tab, p->rk[0], cws, cwv, cwt, np1, KP::make(K, (uint32_t)(nroots << m)), nlev - kFdTail,
+                     (uint32_t)nnodes, (const uint4*)cur, (uint32_t)skip, (uint32_t)n, (uint4*)ys, ctrs + kRangeCtrs - 1,
+                     blocks);
+  HIP_TRY(hipGetLastError());
   return DCF_OK;
 }
 
@@ -2127,58 +2206,18 @@ static int range_launch(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_
   }
   Workspace* w = L.w;
   if (int rc = ensure_ctr(w)) return rc;
-  const uint32_t nlev = (uint32_t)(8 * nb);
-  const uint64_t maxroots = (std::min<uint64_t>(cnt, kRangeLaunch) >> h) + 2;
-  const uint32_t m = h ? h - kRangeTail : 0u;  // breadth-first levels below a root
-  // two ping-pong buffers of rows (32 B) up to level 8N - kRangeTail (4 B per output of a launch
-  // in all), then one work counter per launch
-  const size_t buf_bytes = align256((maxroots * 32) << m), ctr_bytes = 16 * sizeof(uint32_t);
-  if (h)
-    if (int rc = ensure_ws(w, 2 * buf_bytes + ctr_bytes, st)) return rc;
+  size_t buf_bytes;
+  if (const size_t ws = range_ws_bytes(1, std::min<uint64_t>(cnt, kRangeLaunch), h, &buf_bytes))
+    if (int rc = ensure_ws(w, ws, st)) return rc;
   if (zero_blocks) HIP_TRY(hipMemsetAsync(w->d_ctr, 0, kCtrBytes, st));
-  unsigned long long* blocks = reinterpret_cast<unsigned long long*>(w->d_ctr) + 1;
   w->last_prefix = 0;
   phase_mark(p, L, 0);
   phase_mark(p, L, 1);
-  const uint4* cws = (const uint4*)cwb;
-  const uint4* cwv = (const uint4*)(cwb + (size_t)nlev * lam);
-  const uint8_t* cwt = cwb + 2 * (size_t)nlev * lam;
-  const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(nb, lam, 1));
-  const uint64_t cus = (uint64_t)p->cus;
-  if (h == 0) {  // every point is its own root: the root walk writes y
-    hipLaunchKernelGGL(k_range_roots16<true>, dim3((unsigned)std::min<uint64_t>(cus, (cnt + 31) / 32)), dim3(kBlock),
-                       0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, (const uint4*)s0, (uint32_t)party,
-                       range_add(A.x, off), nlev, cnt, (uint4*)ys, blocks);
-    HIP_TRY(hipGetLastError());
-  } else {
-    uint32_t* ctrs = (uint32_t*)(w->d_ws + 2 * buf_bytes);
-    for (uint64_t o = 0; o < cnt; o += kRangeLaunch) {
-      const uint64_t n = std::min<uint64_t>(kRangeLaunch, cnt - o);
-      const RangeX xa = range_add(A.x, off + o);
-      const uint64_t skip = xa.lo & ((1ull << h) - 1);
-      const RangeX pfx{(xa.lo >> h) | (xa.hi << (64 - h)), xa.hi >> h};
-      const uint64_t nroots = ((skip + n - 1) >> h) + 1;  // <= maxroots
-      uint4* cur = (uint4*)w->d_ws;
-      uint4* nxt = (uint4*)(w->d_ws + buf_bytes);
-      HIP_TRY(hipMemsetAsync(ctrs, 0, ctr_bytes, st));
-      hipLaunchKernelGGL(k_range_roots16<false>, dim3((unsigned)std::min<uint64_t>(cus, (nroots + 31) / 32)),
-                         dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, (const uint4*)s0,
-                         (uint32_t)party, pfx, nlev - h, nroots, cur, blocks);
-      HIP_TRY(hipGetLastError());
-      for (uint32_t k = 0; k < m; ++k) {  // level 8N - h + k: nroots << k parents
-        const uint64_t parents = nroots << k;
-        hipLaunchKernelGGL(k_range_level16, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
-                           p->rk[0], cws, cwv, cwt, nlev - h + k, (uint32_t)parents, (const uint4*)cur, nxt,
-                           ctrs + k, blocks);
-        HIP_TRY(hipGetLastError());
-        std::swap(cur, nxt);
-      }
-      const uint64_t nnodes = nroots << m;
-      hipLaunchKernelGGL(k_range_tail16<(int)kRangeTail>, dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock), 0,
-                         st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, nlev - kRangeTail, (uint32_t)nnodes,
-                         (const uint4*)cur, (uint32_t)skip, (uint32_t)n, (uint4*)(ys + o * lam), ctrs + 15, blocks);
-      HIP_TRY(hipGetLastError());
-    }
+  for (uint64_t o = 0; o < cnt; o += kRangeLaunch) {  // h = 0: cnt < 2^12, one pass
+    const uint64_t n = std::min<uint64_t>(kRangeLaunch, cnt - o);
+    if (int rc = range_group<RangeOneKey>(p, L, nb, 1, party, cwb, s0, 0, 1, range_add(A.x, off + o), n, h, buf_bytes,
+                                          ys + o * lam))
+      return rc;
   }
   phase_mark(p, L, 2);
   p->last_ws.store(w);
@@ -2187,10 +2226,7 @@ static int range_launch(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_
 
 int dcf_eval_range_device(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
                           const uint8_t* x0, uint64_t count, uint8_t* ys, void* stream) {
-  if (!p) return fail(DCF_ERR_ARG, "null prg");
-  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
-  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
-  if (!cwb || !s0 || !x0) return fail(DCF_ERR_ARG, "null argument");
+  if (int rc = check_range_args(p, n_bytes, party, cwb, s0, x0)) return rc;
   if (count == 0) return DCF_OK;
   if (!ys) return fail(DCF_ERR_ARG, "null buffer");
   RangeArg A;
@@ -2228,9 +2264,7 @@ static int host_range(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t*
 
 int dcf_eval_range(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, size_t cwb_len, const uint8_t* s0,
                    const uint8_t* x0, uint64_t count, uint8_t* ys, size_t ys_len) {
-  if (!p || !cwb || !s0 || !x0) return fail(DCF_ERR_ARG, "null argument");
-  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
-  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
+  if (int rc = check_range_args(p, n_bytes, party, cwb, s0, x0)) return rc;
   const size_t lam = p->lambda;
   if (cwb_len != dcf_cwb_bytes(n_bytes, lam, 1))
     return fail(DCF_ERR_KEY, "key size does not match 8*N levels (lib.rs:165)");
@@ -2247,17 +2281,17 @@ int dcf_eval_range(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, si
   return host_finish(L, rc);
 }
 
-// ---- multi-key contiguous-range eval (kernels_range_mk.h; DESIGN.md "Multi-key range eval") ----
+// ---- multi-key contiguous-range eval (kernels_range.h; DESIGN.md "Multi-key range eval") ----
 
 constexpr uint64_t kRangeMkDirectMax = 1ull << 12;  // fewer outputs than this in the whole call: h = 0
 
 // Height of the aligned blocks the multi-key tree path uses (documented in include/dcf_hip.h).
 static uint32_t rangemk_levels(size_t n_bytes, uint64_t num_keys, uint64_t count) {
-  if (count < (4ull << kRangeTail)) return 0;  // 2^h <= count / 4 needs h >= kRangeTail = 4
+  if (count < (4ull << kFdTail)) return 0;  // 2^h <= count / 4 needs h >= kFdTail = 4
   const uint64_t small = (kRangeMkDirectMax + count - 1) / count;  // K * count < 2^12 <=> K < ceil(2^12 / count)
   if (num_keys < small) return 0;
   const uint32_t lg = 63u - (uint32_t)__builtin_clzll(count);
-  const uint32_t h = std::min<uint32_t>(kRangeMaxH, lg - 2u);  // >= kRangeTail: count >= 64
+  const uint32_t h = std::min<uint32_t>(kRangeMaxH, lg - 2u);  // >= kFdTail: count >= 64
   return (uint32_t)std::min<uint64_t>(h, 8 * (uint64_t)n_bytes);
 }
 
@@ -2275,61 +2309,6 @@ int dcf_eval_range_multikey_subtree_levels(size_t n_bytes, size_t num_keys, uint
 size_t dcf_eval_range_keys_per_launch(size_t n_bytes, size_t num_keys, uint64_t count) {
   if (!n_bytes || !count) return 1;
   return (size_t)rangemk_keys_per_launch(rangemk_levels(n_bytes, std::max<size_t>(num_keys, 1), count), count);
-}
-
-// One launch group of the tree path: keys [key0, key0 + keys) over the n <= 2^28 points from xa,
-// keys * n <= 2^28; the outputs of key key0 + k go to rows [k * n, (k + 1) * n) of ys (several keys
-// in a group: n is the call's count).
-static int rangemk_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb, const uint8_t* s0s,
-                         uint64_t key0, uint64_t keys, const RangeX xa, uint64_t n, uint32_t h, size_t buf_bytes,
-                         uint8_t* ys) {
-  hipStream_t st = L.st;
-  Workspace* w = L.w;
-  const size_t lam = 16;
-  const uint32_t nlev = (uint32_t)(8 * nb);
-  const uint4* cws = (const uint4*)cwb + key0;
-  const uint4* cwv = (const uint4*)(cwb + (size_t)nlev * K * lam) + key0;
-  const uint8_t* cwt = cwb + 2 * (size_t)nlev * K * lam + key0;
-  const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(nb, lam, K)) + key0;
-  const uint4* s0 = (const uint4*)s0s + key0;
-  unsigned long long* blocks = reinterpret_cast<unsigned long long*>(w->d_ctr) + 1;
-  const uint64_t cus = (uint64_t)p->cus;
-  if (h == 0) {  // every point is its own root: the root walk writes y
-    const uint64_t total = keys * n;
-    hipLaunchKernelGGL(k_rangemk_roots16<true>, dim3((unsigned)std::min<uint64_t>(cus, (total + 31) / 32)),
-                       dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, s0, (uint64_t)K, (uint32_t)party,
-                       xa, nlev, range_div_make((uint32_t)n), (uint32_t)total, (uint4*)ys, blocks);
-    HIP_TRY(hipGetLastError());
-    return DCF_OK;
-  }
-  const uint32_t m = h - kRangeTail;  // breadth-first levels below a root
-  const uint64_t skip = xa.lo & ((1ull << h) - 1);
-  const RangeX pfx{(xa.lo >> h) | (xa.hi << (64 - h)), xa.hi >> h};
-  const uint64_t nroots = ((skip + n - 1) >> h) + 1;
-  uint32_t* ctrs = (uint32_t*)(w->d_ws + 2 * buf_bytes);
-  uint4* cur = (uint4*)w->d_ws;
-  uint4* nxt = (uint4*)(w->d_ws + buf_bytes);
-  HIP_TRY(hipMemsetAsync(ctrs, 0, 16 * sizeof(uint32_t), st));
-  const uint64_t total = keys * nroots;
-  hipLaunchKernelGGL(k_rangemk_roots16<false>, dim3((unsigned)std::min<uint64_t>(cus, (total + 31) / 32)),
-                     dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, s0, (uint64_t)K, (uint32_t)party,
-                     pfx, nlev - h, range_div_make((uint32_t)nroots), (uint32_t)total, cur, blocks);
-  HIP_TRY(hipGetLastError());
-  for (uint32_t k = 0; k < m; ++k) {  // level 8N - h + k: nroots << k parents per key
-    const uint64_t parents = total << k;
-    hipLaunchKernelGGL(k_rangemk_level16, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
-                       p->rk[0], cws, cwv, cwt, (uint64_t)K, nlev - h + k, range_div_make((uint32_t)(nroots << k)),
-                       (uint32_t)parents, (const uint4*)cur, nxt, ctrs + k, blocks);
-    HIP_TRY(hipGetLastError());
-    std::swap(cur, nxt);
-  }
-  const uint64_t nnodes = total << m;
-  hipLaunchKernelGGL(k_rangemk_tail16<(int)kRangeTail>, dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock), 0, st,
-                     p->d_tab, p->rk[0], cws, cwv, cwt, np1, (uint64_t)K, nlev - kRangeTail,
-                     range_div_make((uint32_t)(nroots << m)), (uint32_t)nnodes, (const uint4*)cur, (uint32_t)skip,
-                     (uint32_t)n, (uint4*)ys, ctrs + 15, blocks);
-  HIP_TRY(hipGetLastError());
-  return DCF_OK;
 }
 
 // The slow path (MMO PRG, lambda >= 32, N > 16): key by key, each gathered into the single-key
@@ -2356,10 +2335,7 @@ static int rangemk_fallback(dcf_prg* p, Lease& L, size_t nb, size_t K, int party
 
 int dcf_eval_range_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, int party, const uint8_t* cwb,
                                    const uint8_t* s0s, const uint8_t* x0, uint64_t count, uint8_t* ys, void* stream) {
-  if (!p) return fail(DCF_ERR_ARG, "null prg");
-  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
-  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
-  if (!cwb || !s0s || !x0) return fail(DCF_ERR_ARG, "null argument");
+  if (int rc = check_range_args(p, n_bytes, party, cwb, s0s, x0)) return rc;
   if (n_bytes > 16 + kRangeTopMax) return fail(DCF_ERR_UNSUPPORTED, "range eval: N <= 256");
   if (num_keys == 0 || count == 0) return DCF_OK;
   if (!ys) return fail(DCF_ERR_ARG, "null buffer");
@@ -2374,11 +2350,9 @@ int dcf_eval_range_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, 
   if (int rc = ensure_ctr(w)) return rc;
   const uint32_t h = rangemk_levels(n_bytes, num_keys, count);
   const uint64_t per = std::min<uint64_t>(num_keys, rangemk_keys_per_launch(h, count));
-  const uint64_t n1 = std::min<uint64_t>(count, kRangeLaunch);  // outputs of one key in a launch
-  // two ping-pong buffers of rows (32 B) up to level 8N - kRangeTail, then the work counters
-  const size_t buf_bytes = h ? align256((per * ((n1 >> h) + 2) * 32) << (h - kRangeTail)) : 0;
-  if (h)
-    if (int rc = ensure_ws(w, 2 * buf_bytes + 16 * sizeof(uint32_t), L.st)) return rc;
+  size_t buf_bytes;
+  if (const size_t ws = range_ws_bytes(per, std::min<uint64_t>(count, kRangeLaunch), h, &buf_bytes))
+    if (int rc = ensure_ws(w, ws, L.st)) return rc;
   HIP_TRY(hipMemsetAsync(w->d_ctr, 0, kCtrBytes, L.st));
   w->last_prefix = 0;
   phase_mark(p, L, 0);
@@ -2386,7 +2360,7 @@ int dcf_eval_range_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, 
   if ((count >> h) + 2 <= (kRangeLaunch >> h)) {  // groups of whole keys
     for (uint64_t k0 = 0; k0 < num_keys; k0 += per) {
       const uint64_t keys = std::min<uint64_t>(per, num_keys - k0);
-      if (int rc = rangemk_group(p, L, n_bytes, num_keys, party, cwb, s0s, k0, keys, A.x, count, h, buf_bytes,
+      if (int rc = range_group<RangeKeys>(p, L, n_bytes, num_keys, party, cwb, s0s, k0, keys, A.x, count, h, buf_bytes,
                                  ys + k0 * count * 16))
         return rc;
     }
@@ -2394,7 +2368,7 @@ int dcf_eval_range_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, 
     for (uint64_t k = 0; k < num_keys; ++k)
       for (uint64_t o = 0; o < count; o += kRangeLaunch) {
         const uint64_t n = std::min<uint64_t>(kRangeLaunch, count - o);
-        if (int rc = rangemk_group(p, L, n_bytes, num_keys, party, cwb, s0s, k, 1, range_add(A.x, o), n, h, buf_bytes,
+        if (int rc = range_group<RangeKeys>(p, L, n_bytes, num_keys, party, cwb, s0s, k, 1, range_add(A.x, o), n, h, buf_bytes,
                                    ys + (k * count + o) * 16))
           return rc;
       }

@@ -534,6 +534,16 @@ __device__ __forceinline__ void fd_children(const uint32_t* lds, uint32_t lc, co
   tr = ((st[1][0] ^ ~s[0]) & 1u) ^ (t & (ct >> 1) & 1u);
 }
 
+// The correction words of row c of a key block (c = level, or level * K + key) as fd_children takes
+// them; returns cw_t.
+__device__ __forceinline__ uint32_t fd_cw(const uint4* cw_s, const uint4* cw_v, const uint8_t* cw_t, uint64_t c,
+                                          uint32_t (&csw)[4], uint32_t (&cvw)[4]) {
+  const uint4 cs = cw_s[c], cv = cw_v[c];
+  csw[0] = cs.x; csw[1] = cs.y; csw[2] = cs.z; csw[3] = cs.w;
+  cvw[0] = cv.x; cvw[1] = cv.y; cvw[2] = cv.z; cvw[3] = cv.w;
+  return cw_t[c];
+}
+
 // Multi-key top trees: for each of K keys, its PrefixTable rows of depth D (2^D rows per
 // key, row k * 2^D + the point's top D x bits), so a key's points start on level D instead of
 // each walking levels 0..D-1 (C5: 64 points per key share the top of the tree).  Thread

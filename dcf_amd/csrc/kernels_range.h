@@ -1,21 +1,31 @@
-// kernels_range.h — contiguous-range eval: ys[i] = Dcf::eval(b, k, x0 + i), i in [0, count).
+// kernels_range.h — contiguous-range eval: ys[i] = Dcf::eval(b, k, x0 + i), i in [0, count), for one
+// key, and ys[k * count + i] = Dcf::eval(b, key k, x0 + i) for K keys over one range.
 // Included by dcf_hip.hip only (after kernels16.h and kernels_lat.h).
 //
 // Consecutive points share almost their whole GGM path, so the Hirose LAMBDA = 16 path covers the
 // range by the aligned blocks of 2^h leaves that intersect it and expands each block's subtree
-// once: 2 AES blocks per output instead of 16N per point (DESIGN.md "Range eval").
+// once: 2 AES blocks per output instead of 16N per point (DESIGN.md "Range eval", "Multi-key range
+// eval").  Every key's range is covered by the same nroots blocks; every node buffer holds the keys
+// of a launch group one after another, each in leaf order, so node j of a level with d nodes per
+// key belongs to key j / d and key k's outputs are contiguous.
 //   k_range_roots16   the roots of those blocks — the nodes of level 8N - h whose prefixes run
 //                     from x0 >> h upwards — each walked from s0 on a 32-lane half-wave (RowPrg, as
 //                     k_prefix_build16's root path); the path bits come from the 128-bit value
-//                     prefix + root index.  h = 0: the "roots" are the points themselves and the
-//                     kernel writes y (small counts).
-//   k_range_level16   the h - kRangeTail levels below the roots, breadth-first over all blocks at
+//                     prefix + root index.  h = 0 (LEAF): the "roots" are the points themselves and
+//                     the kernel writes y (small counts).
+//   k_range_level16   the h - kFdTail levels below the roots, breadth-first over all blocks at
 //                     once, one launch per level (as k_fd_level16, on 32-byte rows): the nodes of
 //                     all blocks stay consecutive, in leaf order, in two ping-pong buffers.
-//   k_range_tail16    the register depth-first tail of k_fd_dfs16 on those nodes; a leaf's output
-//                     index is its distance from x0 and leaves outside the range are not stored.
+//   k_range_tail16    the register depth-first tail of k_fd_dfs16 on those nodes; a
+//                     leaf's output index is its distance from x0 and leaves outside the range are
+//                     not stored.
+// Each is a template on the key policy, RangeOneKey or RangeKeys, and is instantiated for both.
 //   k_range_points    the points x0 + i as N-byte big-endian strings, for the PRGs / LAMBDA without
 //                     a tree-sharing path (the existing eval runs on them).
+//   k_rangemk_gather  key k of a K-key block as a single-key block (the same slow path, key by key).
+// The pointers the kernels get are already advanced to the first key of the launch group; K stays
+// the row stride.  All node, key and output indices of a tree launch are 32-bit (the host keeps
+// keys * (nroots << h) <= 2^28).
 #pragma once
 
 #include "aes_lds.h"
@@ -38,7 +48,6 @@ __host__ __device__ __forceinline__ uint32_t range_bit(const RangeX a, const uin
   return (uint32_t)((i < 64u ? a.lo >> i : a.hi >> (i - 64u)) & 1u);
 }
 
-constexpr uint32_t kRangeTail = 4;   // depth-first register tail (kFdTail)
 constexpr uint32_t kRangeMaxH = 14;  // at most 10 breadth-first levels above the tail
 constexpr uint32_t kRangeTopMax = 240;  // bytes of x above the low 16 (N <= 256)
 
@@ -47,33 +56,85 @@ struct RangeTop {
   uint8_t b[kRangeTopMax];
 };
 
-// Root r (32 lanes each) is the node of level `nwalk` whose nwalk-bit prefix is pfx + r: walked
-// from (s0, 0, party) with RowPrg, bits Msb-first.  LEAF = false: PrefixTable-style row (s with t
-// in bit 0 of byte 15, then v) to out[2r], out[2r + 1]; the caller keeps nwalk >= 1, so s is
-// masked there.  LEAF = true (nwalk = 8N): y = v ^ s ^ t * cw_np1 (lib.rs:192) to out[r].
+// n / d for n < 2^28 without a division: q = (n * mul) >> sh with sh = 28 + ceil(log2 d) and
+// mul = ceil(2^sh / d) <= 2^29 + 1 (round-up method: mul * d - 2^sh < d <= 2^(sh - 28), so the
+// quotient is exact for every n < 2^28).  Built on the host once per launch.
+struct RangeDiv {
+  uint32_t d, mul, sh;
+};
+__host__ inline RangeDiv range_div_make(const uint32_t d) {  // 1 <= d <= 2^28
+  uint32_t l = 0;
+  while ((1ull << l) < d) ++l;
+  RangeDiv r;
+  r.d = d;
+  r.sh = 28u + l;
+  r.mul = (uint32_t)(((1ull << r.sh) + d - 1u) / d);
+  return r;
+}
+__host__ __device__ __forceinline__ uint32_t range_div(const RangeDiv dv, const uint32_t n) {
+  return (uint32_t)(((uint64_t)n * dv.mul) >> dv.sh);
+}
+
+// Key policies: the key of node (or root) j of a level with `per` nodes per key, j's index within
+// that key, and the row of the key block that holds the key's correction words of level lev.
+//   kPerLane   the lanes of a wave may differ in their key, so correction words, seeds and cw_np1
+//              are per-lane loads inside the work loop; otherwise they are uniform, loaded once
+//              ahead of it and held in scalars.
+//   Idx        the root kernel's index type (a single-key direct walk takes the caller's count).
+struct RangeOneKey {
+  static constexpr bool kPerLane = false;
+  using Idx = uint64_t;
+  static RangeOneKey make(uint64_t, uint32_t) { return {}; }
+  template <class T>
+  __device__ __forceinline__ uint32_t key(T) const { return 0u; }
+  template <class T>
+  __device__ __forceinline__ T node(T j, uint32_t) const { return j; }
+  __device__ __forceinline__ uint64_t cw(uint32_t lev, uint32_t) const { return lev; }
+};
+// Key j / per of the group; its words are a broadcast within one key, coalesced across neighbours.
+struct RangeKeys {
+  static constexpr bool kPerLane = true;
+  using Idx = uint32_t;
+  uint64_t K;  // keys in the block: the row stride
+  RangeDiv per;
+  static RangeKeys make(uint64_t K, uint32_t per) { return {K, range_div_make(per)}; }
+  __device__ __forceinline__ uint32_t key(uint32_t j) const { return range_div(per, j); }
+  __device__ __forceinline__ uint32_t node(uint32_t j, uint32_t key) const { return j - key * per.d; }
+  __device__ __forceinline__ uint64_t cw(uint32_t lev, uint32_t key) const { return (uint64_t)lev * K + key; }
+};
+
+// Root r (32 lanes each) of `total` = keys * per: the node of level `nwalk` of key kp.key(r) whose
+// nwalk-bit prefix is pfx + kp.node(r), walked from (s0s[key], 0, party) with RowPrg, bits
+// Msb-first.  LEAF = false: PrefixTable-style row (s with t in bit 0 of byte 15, then v) to
+// out[2r], out[2r + 1]; the caller keeps nwalk >= 1, so s is masked there.  LEAF = true
+// (nwalk = 8N, per = count, so r = key * count + i): y = v ^ s ^ t * cw_np1 (lib.rs:192) to out[r].
 // blocks: the call's AES block count (dcf_prg_last_eval_blocks), 2 per level and root.
-template <bool LEAF>
+template <bool LEAF, class KP>
 __global__ __launch_bounds__(kBlock, 1) void k_range_roots16(
     const uint32_t* __restrict__ tab, const RoundKeys rk, const uint4* __restrict__ cw_s,
     const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const uint4* __restrict__ cw_np1,
-    const uint4* __restrict__ s0, const uint32_t party, const RangeX pfx, const uint32_t nwalk,
-    const uint64_t nroots, uint4* __restrict__ out, unsigned long long* __restrict__ blocks) {
+    const uint4* __restrict__ s0s, const KP kp, const uint32_t party, const RangeX pfx, const uint32_t nwalk,
+    const typename KP::Idx total, uint4* __restrict__ out, unsigned long long* __restrict__ blocks) {
+  using Idx = typename KP::Idx;
   __shared__ uint32_t lds[kLdsWords];
   lds_fill_tables(lds, tab);
   RowPrg rp;
   rp.init(rk);
   const uint32_t a = rp.a;
-  const uint32_t s0a = reinterpret_cast<const uint32_t*>(s0)[a];
-  const uint32_t npa = reinterpret_cast<const uint32_t*>(cw_np1)[a];
+  const uint32_t s0a = KP::kPerLane ? 0u : reinterpret_cast<const uint32_t*>(s0s)[a];
+  const uint32_t npa = KP::kPerLane ? 0u : reinterpret_cast<const uint32_t*>(cw_np1)[a];
   constexpr uint32_t kPer = kBlock / 32;  // roots per workgroup pass
-  for (uint64_t base = (uint64_t)blockIdx.x * kPer; base < nroots; base += (uint64_t)gridDim.x * kPer) {
-    const uint64_t r = base + (threadIdx.x >> 5);
-    const bool live = r < nroots;
-    const RangeX p = range_add(pfx, live ? r : nroots - 1);
-    uint32_t s = s0a, v = 0u, t = party;
+  for (Idx base = (Idx)blockIdx.x * kPer; base < total; base += (Idx)gridDim.x * kPer) {
+    const Idx r = base + (threadIdx.x >> 5);
+    const bool live = r < total;
+    const Idx rr = live ? r : total - 1u;
+    const uint32_t key = kp.key(rr);
+    const RangeX p = range_add(pfx, kp.node(rr, key));
+    uint32_t s = KP::kPerLane ? reinterpret_cast<const uint32_t*>(s0s + key)[a] : s0a, v = 0u, t = party;
     for (uint32_t lev = 0; lev < nwalk; ++lev) {
-      const uint32_t cs = reinterpret_cast<const uint32_t*>(cw_s + lev)[a];
-      const uint32_t cv = reinterpret_cast<const uint32_t*>(cw_v + lev)[a], ct = cw_t[lev];
+      const uint64_t c = kp.cw(lev, key);
+      const uint32_t cs = reinterpret_cast<const uint32_t*>(cw_s + c)[a];
+      const uint32_t cv = reinterpret_cast<const uint32_t*>(cw_v + c)[a], ct = cw_t[c];
       uint32_t sl, vl, tl, sr, vr, tr;
       rp.children(lds, s, v, t, cs, cv, ct, sl, vl, tl, sr, vr, tr);
       const bool right = range_bit(p, nwalk - 1u - lev) != 0u;
@@ -81,13 +142,13 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_roots16(
       v = right ? vr : vl;
       t = right ? tr : tl;
     }
-    if (threadIdx.x == 0)
-      atomicAdd(blocks, 2ull * nwalk * (unsigned long long)min((uint64_t)kPer, nroots - base));
+    if (threadIdx.x == 0) atomicAdd(blocks, 2ull * nwalk * (unsigned long long)min((Idx)kPer, total - base));
     if (live && (threadIdx.x & 31u) < 4u) {  // row 0, lanes 0..3: columns 0..3
       if (LEAF) {
-        reinterpret_cast<uint32_t*>(out + r)[a] = v ^ s ^ ((0u - t) & npa);
+        const uint32_t np = KP::kPerLane ? reinterpret_cast<const uint32_t*>(cw_np1 + key)[a] : npa;
+        reinterpret_cast<uint32_t*>(out + r)[a] = v ^ s ^ ((0u - t) & np);
       } else {
-        uint32_t* o = reinterpret_cast<uint32_t*>(out + 2u * r);
+        uint32_t* o = reinterpret_cast<uint32_t*>(out + 2ull * r);
         o[a] = a == 3u ? ((s & kMaskLast) | (t << 24)) : s;
         o[4u + a] = v;
       }
@@ -96,20 +157,20 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_roots16(
 }
 
 // Interior, one launch per level (k_fd_level16 on PrefixTable-style rows): the parents of level
-// `lev` — rows in[2j], in[2j + 1] of all blocks, consecutive in leaf order — become the children
-// rows out[4j .. 4j + 3], one lane per parent, waves claiming units of parents from ctr[0].
-// blocks: the call's AES block count, 2 per parent.
+// `lev` — rows in[2j], in[2j + 1] of all blocks of all keys, consecutive in leaf order — become the
+// children rows out[4j .. 4j + 3], one lane per parent, waves claiming units of parents from
+// ctr[0].  blocks: the call's AES block count, 2 per parent.
+template <class KP>
 __global__ __launch_bounds__(kBlock, 1) void k_range_level16(
     const uint32_t* __restrict__ tab, const RoundKeys rk, const uint4* __restrict__ cw_s,
-    const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const uint32_t lev,
+    const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const KP kp, const uint32_t lev,
     const uint32_t nparents, const uint4* __restrict__ in, uint4* __restrict__ out, uint32_t* __restrict__ ctr,
     unsigned long long* __restrict__ blocks) {
   __shared__ uint32_t lds[kLdsWords];
   lds_fill_tables(lds, tab);
   const uint32_t lc = lane_const();
-  const uint4 cs = cw_s[lev], cv = cw_v[lev];
-  const uint32_t csw[4] = {cs.x, cs.y, cs.z, cs.w}, cvw[4] = {cv.x, cv.y, cv.z, cv.w};
-  const uint32_t ct = cw_t[lev];
+  uint32_t csw[4], cvw[4], ct = 0u;
+  if constexpr (!KP::kPerLane) ct = fd_cw(cw_s, cw_v, cw_t, kp.cw(lev, 0u), csw, cvw);
   const uint32_t unit = fd_unit(nparents);
   uint32_t nlive = 0;  // parents this wave expanded: one atomic per wave, after its last unit
   for (uint64_t base = next_unit_base_n(ctr, ~0ull, unit); base < nparents;
@@ -118,6 +179,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_level16(
     const bool live = j < nparents;
     const uint32_t jj = live ? j : nparents - 1u;
     nlive += (uint32_t)__popcll(__ballot(live));
+    if constexpr (KP::kPerLane) ct = fd_cw(cw_s, cw_v, cw_t, kp.cw(lev, kp.key(jj)), csw, cvw);
     const uint4 a = in[2ull * jj], b = in[2ull * jj + 1u];
     const uint32_t s[4] = {a.x, a.y, a.z, a.w & kMaskLast}, v[4] = {b.x, b.y, b.z, b.w};
     uint32_t sl[4], vl[4], sr[4], vr[4], tl, tr;
@@ -133,23 +195,30 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_level16(
 }
 
 // Tail: k_fd_dfs16's register depth-first expansion of the last H levels from the rows of level
-// lev0 = 8N - H, one lane per node, waves claiming units of nodes from ctr[0].  Node j's leaves
-// are g = (j << H) .. (j << H) + 2^H - 1, counted from the first root's first leaf; the range
-// starts `skip` leaves in and holds `count`, so leaf g is output g - skip and is stored only when
-// that is below count (32-bit: a launch covers at most 2^28 outputs; g < skip wraps far above).
+// lev0 = 8N - H, one lane per node, waves claiming units of nodes from ctr[0] (the stack logic is
+// written out here as there: a function template shared by the two compiled to 3 % more VALU work
+// in the expansion loop and measured 3 % slower, profiles/AB_LOG.md round 8).  Node j is node kp.node(j) of key kp.key(j); its leaves are g = (node << H) ..
+// (node << H) + 2^H - 1 of that key, counted from the first root's first leaf; the range starts
+// `skip` leaves in and holds `count`, so leaf g is the key's output g - skip, stored at
+// ys[key * count + g - skip] only when g - skip is below count (32-bit: a launch covers at most
+// 2^28 outputs; g < skip wraps far above).
+// PACKED (per-lane correction words): the node and the stack slots stay in the rows' form, 8 words
+// with t in bit 24 of word 3, the bit s has cleared; the words take the registers that a separate t
+// (9-word nodes) has otherwise.
 // blocks: the call's AES block count, 2 (2^H - 1) per node — clipped leaves included.
-template <int H>
+template <int H, class KP>
 __global__ __launch_bounds__(kBlock, 1) void k_range_tail16(
     const uint32_t* __restrict__ tab, const RoundKeys rk, const uint4* __restrict__ cw_s,
     const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const uint4* __restrict__ cw_np1,
-    const uint32_t lev0, const uint32_t nnodes, const uint4* __restrict__ rows, const uint32_t skip,
+    const KP kp, const uint32_t lev0, const uint32_t nnodes, const uint4* __restrict__ rows, const uint32_t skip,
     const uint32_t count, uint4* __restrict__ ys, uint32_t* __restrict__ ctr,
     unsigned long long* __restrict__ blocks) {
   static_assert(H >= 2 && H <= 4, "register depth-first tail of 2..4 levels");
+  constexpr bool PACKED = KP::kPerLane;
   __shared__ uint32_t lds[kLdsWords];
   lds_fill_tables(lds, tab);
   const uint32_t lc = lane_const();
-  const uint4 np = cw_np1[0];
+  const uint4 np0 = KP::kPerLane ? make_uint4(0u, 0u, 0u, 0u) : cw_np1[0];
   const uint32_t unit = fd_unit(nnodes);
   uint32_t nlive = 0;  // nodes this wave expanded: one atomic per wave, after its last unit
   for (uint64_t base = next_unit_base_n(ctr, ~0ull, unit); base < nnodes;
@@ -158,15 +227,18 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_tail16(
     const bool live = j < nnodes;
     const uint32_t jj = live ? j : nnodes - 1u;
     nlive += (uint32_t)__popcll(__ballot(live));
-    uint32_t stk[H - 1][9];  // pending right children: s[4] | v[4] | t, by depth
-    uint32_t n[9];
+    const uint32_t key = kp.key(jj);
+    constexpr int W = PACKED ? 8 : 9;
+    uint32_t stk[H - 1][W];  // pending right children, by depth
+    uint32_t n[W];
     {
       const uint4 sv = rows[2ull * jj], vv = rows[2ull * jj + 1u];
-      n[0] = sv.x; n[1] = sv.y; n[2] = sv.z; n[3] = sv.w & kMaskLast;
+      n[0] = sv.x; n[1] = sv.y; n[2] = sv.z; n[3] = PACKED ? sv.w : sv.w & kMaskLast;
       n[4] = vv.x; n[5] = vv.y; n[6] = vv.z; n[7] = vv.w;
-      n[8] = (sv.w >> 24) & 1u;
+      if constexpr (!PACKED) n[8] = (sv.w >> 24) & 1u;
     }
-    const uint32_t o0 = live ? (jj << H) - skip : 0x80000000u;  // output of the node's first leaf; idle lanes: none
+    // output of the node's first leaf within its key; idle lanes: none
+    const uint32_t o0 = live ? (kp.node(jj, key) << H) - skip : 0x80000000u;
     for (uint32_t i = 0; i < (1u << (H - 1)); ++i) {
       uint32_t k = 0;
       if (i) {  // resume at the right child saved at depth H - 2 - ctz(i) (wave-uniform)
@@ -175,23 +247,29 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_tail16(
         for (uint32_t q = 0; q + 1 < (uint32_t)H; ++q)
           if (q == d)
 #pragma unroll
-            for (int e = 0; e < 9; ++e) n[e] = stk[q][e];
+            for (int e = 0; e < W; ++e) n[e] = stk[q][e];
         k = d + 1u;
       }
       for (;; ++k) {  // expand depth k (level lev0 + k)
-        const uint4 cs = cw_s[lev0 + k], cv = cw_v[lev0 + k];
+        const uint64_t c = kp.cw(lev0 + k, key);
+        const uint4 cs = cw_s[c], cv = cw_v[c];
         const uint32_t csw[4] = {cs.x, cs.y, cs.z, cs.w}, cvw[4] = {cv.x, cv.y, cv.z, cv.w};
-        const uint32_t s[4] = {n[0], n[1], n[2], n[3]}, v[4] = {n[4], n[5], n[6], n[7]};
+        const uint32_t s[4] = {n[0], n[1], n[2], PACKED ? n[3] & kMaskLast : n[3]}, v[4] = {n[4], n[5], n[6], n[7]};
+        uint32_t t;
+        if constexpr (PACKED) t = (n[3] >> 24) & 1u;
+        else t = n[8];
         uint32_t sl[4], vl[4], sr[4], vr[4], tl, tr;
-        fd_children(lds, lc, rk, csw, cvw, cw_t[lev0 + k], s, v, n[8], sl, vl, tl, sr, vr, tr);
+        fd_children(lds, lc, rk, csw, cvw, cw_t[c], s, v, t, sl, vl, tl, sr, vr, tr);
         if (k + 1u == (uint32_t)H) {  // leaves 2i, 2i + 1 of the node: y = v ^ s ^ t * cw_np1 (lib.rs:192)
           const uint32_t ol = o0 + 2u * i, orr = ol + 1u;
           const uint32_t ml = 0u - tl, mr = 0u - tr;
+          const uint4 np = KP::kPerLane ? cw_np1[key] : np0;
+          uint4* const yk = ys + (uint64_t)key * count;
           if (ol < count)
-            ys[ol] = make_uint4(vl[0] ^ sl[0] ^ (ml & np.x), vl[1] ^ sl[1] ^ (ml & np.y),
+            yk[ol] = make_uint4(vl[0] ^ sl[0] ^ (ml & np.x), vl[1] ^ sl[1] ^ (ml & np.y),
                                 vl[2] ^ sl[2] ^ (ml & np.z), vl[3] ^ sl[3] ^ (ml & np.w));
           if (orr < count)
-            ys[orr] = make_uint4(vr[0] ^ sr[0] ^ (mr & np.x), vr[1] ^ sr[1] ^ (mr & np.y),
+            yk[orr] = make_uint4(vr[0] ^ sr[0] ^ (mr & np.x), vr[1] ^ sr[1] ^ (mr & np.y),
                                  vr[2] ^ sr[2] ^ (mr & np.z), vr[3] ^ sr[3] ^ (mr & np.w));
           break;
         }
@@ -200,17 +278,17 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_tail16(
           if (q == k) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              stk[q][e] = sr[e];
+              stk[q][e] = PACKED && e == 3 ? ((sr[3] & kMaskLast) | (tr << 24)) : sr[e];
               stk[q][4 + e] = vr[e];
             }
-            stk[q][8] = tr;
+            if constexpr (!PACKED) stk[q][8] = tr;
           }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          n[e] = sl[e];
+          n[e] = PACKED && e == 3 ? ((sl[3] & kMaskLast) | (tl << 24)) : sl[e];
           n[4 + e] = vl[e];
         }
-        n[8] = tl;
+        if constexpr (!PACKED) n[8] = tl;
       }
     }
   }
@@ -229,6 +307,31 @@ __global__ void k_range_points(const uint32_t nbytes, const RangeX x0, const Ran
     for (uint32_t b = 0; b < nbytes; ++b) {
       const uint32_t pos = nbytes - 1u - b;  // significance of byte b
       o[b] = pos < 8u ? (uint8_t)(x.lo >> (8u * pos)) : (pos < 16u ? (uint8_t)(x.hi >> (8u * (pos - 8u))) : top.b[b]);
+    }
+  }
+}
+
+// Key `key` of a K-key correction-word block as a single-key block at `out` (np1 at byte `np1_off`
+// of it) and its seed at s0_out: nlev rows of lam bytes of cw_s and cw_v, nlev bytes of cw_t.
+__global__ void k_rangemk_gather(const uint8_t* __restrict__ cwb, const uint8_t* __restrict__ np1,
+                                 const uint8_t* __restrict__ s0s, const uint64_t K, const uint64_t key,
+                                 const uint32_t nlev, const uint32_t lam, const uint32_t np1_off,
+                                 uint8_t* __restrict__ out, uint8_t* __restrict__ s0_out) {
+  const uint32_t rows = nlev * lam;  // bytes of one key's cw_s (and cw_v)
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < 2u * rows + nlev + 2u * lam;
+       i += gridDim.x * blockDim.x) {
+    if (i < 2u * rows) {  // cw_s then cw_v: byte b of level lev
+      const uint32_t part = i / rows, lev = (i % rows) / lam, b = i % lam;
+      out[i] = cwb[((uint64_t)part * nlev * K + (uint64_t)lev * K + key) * lam + b];
+    } else if (i < 2u * rows + nlev) {
+      const uint32_t lev = i - 2u * rows;
+      out[i] = cwb[2ull * nlev * K * lam + (uint64_t)lev * K + key];
+    } else if (i < 2u * rows + nlev + lam) {
+      const uint32_t b = i - (2u * rows + nlev);
+      out[np1_off + b] = np1[key * lam + b];
+    } else {
+      const uint32_t b = i - (2u * rows + nlev + lam);
+      s0_out[b] = s0s[key * lam + b];
     }
   }
 }

@@ -41,6 +41,7 @@
 #include "kernels_mmo_wide.h"
 #include "kernels_wide_stream.h"
 #include "kernels_range.h"
+#include "kernels_range_mmo.h"
 
 namespace {
 
@@ -2127,9 +2128,17 @@ static size_t range_ws_bytes(uint64_t keys, uint64_t n, uint32_t h, size_t* buf_
   return h ? 2 * *buf_bytes + kRangeCtrs * sizeof(uint32_t) : 0;
 }
 
-// One launch group of the tree path (Hirose, lambda = 16, N <= 16): keys [key0, key0 + keys) of a
-// K-key block over the n <= 2^28 points from xa, keys * n <= 2^28; the outputs of key key0 + k go
-// to rows [k * n, (k + 1) * n) of ys (several keys in a group: n is the call's count).  KP: the
+// A launch of the tree path's kernel for the prg's PRG: kh (Hirose, round keys by value) or km
+// (MMO, the AES-128 schedules on the device); both take the T-tables first and `a` after the keys.
+extern "C++" template <class KH, class KM, class... A>
+static void range_run(const dcf_prg* p, hipStream_t st, KH kh, KM km, uint64_t grid, A... a) {
+  if (p->kind == 0) hipLaunchKernelGGL(kh, dim3((unsigned)grid), dim3(kBlock), 0, st, p->d_tab, p->rk[0], a...);
+  else hipLaunchKernelGGL(km, dim3((unsigned)grid), dim3(kBlock), 0, st, p->d_tab, (const uint4*)p->d_rk128, a...);
+}
+
+// One launch group of the tree path (Hirose or MMO, lambda = 16, N <= 16): keys [key0, key0 + keys)
+// of a K-key block over the n <= 2^28 points from xa, keys * n <= 2^28; the outputs of key key0 + k
+// go to rows [k * n, (k + 1) * n) of ys (several keys in a group: n is the call's count).  KP: the
 // kernels' key policy — RangeOneKey takes key0 = 0, keys = K = 1.  The caller has sized the
 // workspace (range_ws_bytes) and zeroed the block count.
 extern "C++" template <class KP>
@@ -2148,11 +2157,13 @@ static int range_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, con
   const uint4* s0 = (const uint4*)s0s + key0;
   unsigned long long* blocks = reinterpret_cast<unsigned long long*>(w->d_ctr) + 1;
   const uint64_t cus = (uint64_t)p->cus;
+  // roots per workgroup before a second one pays: a pass of half-waves (RowPrg), or one wave of lanes (MMO)
+  const uint64_t rper = p->kind == 0 ? kBlock / 32 : 64;
   if (h == 0) {  // every point is its own root: the root walk writes y
     const uint64_t total = keys * n;
-    hipLaunchKernelGGL((k_range_roots16<true, KP>), dim3((unsigned)std::min<uint64_t>(cus, (total + 31) / 32)),
-                       dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, s0, KP::make(K, (uint32_t)n),
-                       (uint32_t)party, xa, nlev, (Idx)total, (uint4*)ys, blocks);
+    range_run(p, st, k_range_roots16<true, KP>, k_range_roots16_mmo<true, KP>,
+              std::min<uint64_t>(cus, (total + rper - 1) / rper), cws, cwv, cwt, np1, s0,
+              KP::make(K, (uint32_t)n), (uint32_t)party, xa, nlev, (Idx)total, (uint4*)ys, blocks);
     HIP_TRY(hipGetLastError());
     return DCF_OK;
   }
@@ -2165,23 +2176,22 @@ static int range_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, con
   uint4* nxt = (uint4*)(w->d_ws + buf_bytes);
   HIP_TRY(hipMemsetAsync(ctrs, 0, kRangeCtrs * sizeof(uint32_t), st));
   const uint64_t total = keys * nroots;
-  hipLaunchKernelGGL((k_range_roots16<false, KP>), dim3((unsigned)std::min<uint64_t>(cus, (total + 31) / 32)),
-                     dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1, s0, KP::make(K, (uint32_t)nroots),
-                     (uint32_t)party, pfx, nlev - h, (Idx)total, cur, blocks);
+  range_run(p, st, k_range_roots16<false, KP>, k_range_roots16_mmo<false, KP>,
+            std::min<uint64_t>(cus, (total + rper - 1) / rper), cws, cwv, cwt, np1, s0,
+            KP::make(K, (uint32_t)nroots), (uint32_t)party, pfx, nlev - h, (Idx)total, cur, blocks);
   HIP_TRY(hipGetLastError());
   for (uint32_t k = 0; k < m; ++k) {  // level 8N - h + k: nroots << k parents per key
     const uint64_t parents = total << k;
-    hipLaunchKernelGGL(k_range_level16<KP>, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
-                       p->rk[0], cws, cwv, cwt, KP::make(K, (uint32_t)(nroots << k)), nlev - h + k, (uint32_t)parents,
-                       (const uint4*)cur, nxt, ctrs + k, blocks);
+    range_run(p, st, k_range_level16<KP>, k_range_level16_mmo<KP>, grid_for(parents, p->cus), cws, cwv, cwt,
+              KP::make(K, (uint32_t)(nroots << k)), nlev - h + k, (uint32_t)parents, (const uint4*)cur, nxt, ctrs + k,
+              blocks);
     HIP_TRY(hipGetLastError());
     std::swap(cur, nxt);
   }
   const uint64_t nnodes = total << m;
-  hipLaunchKernelGGL((k_range_tail16<(int)kFdTail, KP>), dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock), 0, st,
-                     p->d_tab, p->rk[0], cws, cwv, cwt, np1, KP::make(K, (uint32_t)(nroots << m)), nlev - kFdTail,
-                     (uint32_t)nnodes, (const uint4*)cur, (uint32_t)skip, (uint32_t)n, (uint4*)ys, ctrs + kRangeCtrs - 1,
-                     blocks);
+  range_run(p, st, k_range_tail16<(int)kFdTail, KP>, k_range_tail16_mmo<(int)kFdTail, KP>, grid_for(nnodes, p->cus), cws,
+            cwv, cwt, np1, KP::make(K, (uint32_t)(nroots << m)), nlev - kFdTail, (uint32_t)nnodes, (const uint4*)cur,
+            (uint32_t)skip, (uint32_t)n, (uint4*)ys, ctrs + kRangeCtrs - 1, blocks);
   HIP_TRY(hipGetLastError());
   return DCF_OK;
 }
@@ -2192,7 +2202,7 @@ static int range_launch(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_
                         const RangeArg& A, uint64_t off, uint64_t cnt, uint32_t h, uint8_t* ys, bool zero_blocks) {
   hipStream_t st = L.st;
   const size_t lam = p->lambda;
-  if (p->kind != 0 || lam != 16 || nb > 16) {  // no tree-sharing path: materialise the points, run eval
+  if (lam != 16 || nb > 16) {  // no tree-sharing path: materialise the points, run eval
     DevBuf xs;  // eval owns the workspace, so the points get their own buffer
     const uint64_t chunk = std::min<uint64_t>(cnt, kRangeChunk);
     HIP_TRY(xs.alloc(chunk * nb));
@@ -2311,7 +2321,7 @@ size_t dcf_eval_range_keys_per_launch(size_t n_bytes, size_t num_keys, uint64_t 
   return (size_t)rangemk_keys_per_launch(rangemk_levels(n_bytes, std::max<size_t>(num_keys, 1), count), count);
 }
 
-// The slow path (MMO PRG, lambda >= 32, N > 16): key by key, each gathered into the single-key
+// The slow path (lambda >= 32, N > 16): key by key, each gathered into the single-key
 // layout in a buffer of the call's own and run through the single-key range path.
 static int rangemk_fallback(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb,
                             const uint8_t* s0s, const RangeArg& A, uint64_t count, uint8_t* ys) {
@@ -2344,7 +2354,7 @@ int dcf_eval_range_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, 
   DeviceGuard dg(p->device);
   Lease L(p);
   if (int rc = L.order((hipStream_t)stream)) return rc;
-  if (p->kind != 0 || p->lambda != 16 || n_bytes > 16)
+  if (p->lambda != 16 || n_bytes > 16)
     return rangemk_fallback(p, L, n_bytes, num_keys, party, cwb, s0s, A, count, ys);
   Workspace* w = L.w;
   if (int rc = ensure_ctr(w)) return rc;

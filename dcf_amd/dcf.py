@@ -407,8 +407,9 @@ class DcfImpl:
 
     def eval_range_device(self, b: bool, cwb, s0, x0, count: int, ys=None):
         """`Dcf::eval` at x0 + i for i in [0, count) (x0: int or N big-endian bytes): the rows
-        eval_device returns over those points, as a (count, LAMBDA) device tensor.  Hirose
-        LAMBDA = 16: tree expansion, 2 AES blocks per output."""
+        eval_device returns over those points, as a (count, LAMBDA) device tensor.
+        LAMBDA = 16, N <= 16: tree expansion, 2 AES-256 blocks per output with the Hirose PRG, 4 AES-128
+        blocks with the MMO PRG; asynchronous on the current stream for both."""
         import torch
         lam, nb, dev = self.lam, self.n_bytes, self.prg.device
         xb = self._x0(x0)
@@ -436,7 +437,8 @@ class DcfImpl:
     def eval_range_multikey_device(self, b: bool, cwb, s0s, x0, count: int, ys=None):
         """K keys over one range: `Dcf::eval` of key k at x0 + i for i in [0, count), as a
         (K, count, LAMBDA) device tensor.  cwb: the K-key block of gen_batch_device, s0s (K, LAMBDA).
-        Hirose LAMBDA = 16, N <= 16: one tree expansion over all keys, 2 AES blocks per output."""
+        LAMBDA = 16, N <= 16: one tree expansion over all keys, 2 AES-256 blocks per output with the
+        Hirose PRG, 4 AES-128 blocks with the MMO PRG; asynchronous on the current stream for both."""
         import torch
         lam, nb, dev = self.lam, self.n_bytes, self.prg.device
         xb = self._x0(x0)

@@ -222,7 +222,8 @@ class DcfImpl final : public Dcf<N, LAMBDA> {
 
   // Dcf::eval over the consecutive points x0 + i, i in [0, count) (x0 big-endian, lib.rs:181):
   // ys = count * LAMBDA bytes, the rows eval returns for those points in order (dcf_eval_range:
-  // tree expansion, 2 AES blocks per output at LAMBDA = 16).  x0 + count may not exceed 2^(8N).
+  // tree expansion at LAMBDA = 16, 2 AES-256 blocks per output with the Hirose PRG, 4 AES-128
+  // blocks with the MMO PRG).  x0 + count may not exceed 2^(8N).
   void eval_range(bool b, const Share<LAMBDA>& k, const std::array<uint8_t, N>& x0, uint64_t count,
                   uint8_t* ys) const {
     if (k.s0s.empty()) throw Error(DCF_ERR_KEY, "k.s0s is empty (lib.rs:168 reads s0s[0])");

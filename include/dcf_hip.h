@@ -311,7 +311,14 @@ int dcf_eval_full_domain_device(dcf_prg* prg, size_t n_bytes, int party, const u
  *   a launch in all.
  *   dcf_prg_last_eval_blocks then reports the AES blocks of the root paths, the interior
  *   expansion and the tail, clipped leaves of the edge blocks included.
- *   Otherwise (MMO PRG, lambda >= 32, N > 16) the points are materialised on the device, 2^22 at a
+ *   MMO PRG, lambda = 16, N <= 16: the same blocks, heights, launches and workspace with the MMO
+ *   kernels (kernels_range_mmo.h); a node's two children cost four AES-128 blocks and a step of a
+ *   root walk two, so 4 AES-128 blocks per output plus 2 (8N - h) per root instead of 32N per
+ *   point, and h = 0 walks every point in one launch.  Asynchronous on `stream` like the Hirose
+ *   path: no materialised points, no stream wait.  dcf_prg_last_eval_blocks then reports the
+ *   executed AES-128 blocks: nroots (2 (8N - h) + 4 (2^h - 1)) per launch, clipped leaves
+ *   included, and 2 * 8N * count at h = 0.
+ *   Otherwise (lambda >= 32, N > 16) the points are materialised on the device, 2^22 at a
  *   time, and dcf_eval_device's path runs on them; that path waits for the stream before returning.
  * Errors, nothing launched: x0 + count > 2^(8N) -> DCF_ERR_ARG; bad party / null pointer ->
  * DCF_ERR_ARG; n_bytes == 0 -> DCF_ERR_N; N > 256 -> DCF_ERR_UNSUPPORTED.  count == 0 -> DCF_OK,
@@ -356,7 +363,12 @@ int dcf_eval_range_subtree_levels(size_t n_bytes, uint64_t count);
  *   above the leaves of a group (at most 2 x 512 MiB).  dcf_prg_last_eval_blocks then reports the
  *   AES blocks of the root paths, the interior levels and the tail, clipped leaves included, summed
  *   over all keys and groups.
- *   Otherwise (MMO PRG, lambda >= 32, N > 16) — the slow path: key by key, each gathered into the
+ *   MMO PRG, lambda = 16, N <= 16: the same blocks, heights, launch groups and workspace with the
+ *   MMO kernels: 4 AES-128 blocks per output plus 2 (8N - h) per root, h = 0 in one launch over all
+ *   (key, point) pairs.  Asynchronous on `stream` like the Hirose path: no key-by-key gather, no
+ *   stream wait.  dcf_prg_last_eval_blocks then reports the executed AES-128 blocks,
+ *   keys * nroots (2 (8N - h) + 4 (2^h - 1)) per group, and 2 * 8N * K * count at h = 0.
+ *   Otherwise (lambda >= 32, N > 16) — the slow path: key by key, each gathered into the
  *   single-key layout and run through dcf_eval_range_device's path; it waits for the stream.
  * Errors, nothing launched: null prg / cwb / s0s / x0, null ys with work to do, bad party ->
  * DCF_ERR_ARG; n_bytes == 0 -> DCF_ERR_N; N > 256 -> DCF_ERR_UNSUPPORTED; x0 + count > 2^(8N) ->

@@ -138,8 +138,9 @@ impl<const N: usize, const LAMBDA: usize> DcfHip<N, LAMBDA> {
 
     /// `Dcf::eval` over the consecutive points `x0 + i`, `i` in `[0, count)` (`x0` big-endian, as
     /// lib.rs:181 reads a point): the rows `eval` returns for those points, in order, as one
-    /// `count * LAMBDA` byte vector (`dcf_eval_range`: tree expansion, 2 AES blocks per output at
-    /// `LAMBDA = 16`).  `x0 + count` may not exceed `2^(8N)`.
+    /// `count * LAMBDA` byte vector (`dcf_eval_range`: tree expansion at `LAMBDA = 16`, 2 AES-256
+    /// blocks per output with the Hirose PRG, 4 AES-128 blocks with the MMO PRG).  `x0 + count` may
+    /// not exceed `2^(8N)`.
     pub fn eval_range(&self, b: bool, k: &Share<LAMBDA>, x0: &[u8; N], count: u64) -> Result<Vec<u8>, DcfHipError> {
         let cwb = share_to_cwb::<N, LAMBDA>(k);
         let mut yb = vec![0u8; count as usize * LAMBDA];

@@ -1,22 +1,25 @@
-"""Multi-key contiguous-range eval (dcf_eval_range_multikey_device) on one MI355X, Hirose PRG,
-LAMBDA = 16, keys from gen_batch_device.
+"""Multi-key contiguous-range eval (dcf_eval_range_multikey_device) on one MI355X, Hirose or MMO PRG
+(--prg), LAMBDA = 16, keys from gen_batch_device.
 
 Shapes:
   N = 1  whole domain (256 points),            K = 2^20
   N = 2  whole domain (2^16 points),           K = 2^12
   N = 16 count = 2^12 at a random odd x0,      K = 2^12
 For each: outputs/s, AES blocks per output (dcf_prg_last_eval_blocks, counted on the device) and the
-executed blocks/s as a fraction of the T-table LDS bound (87.77e9 blocks/s).  Baselines in the same
+executed blocks/s as a fraction of the T-table LDS bound (256 CUs x 32 lookups/clk x 2.4 GHz over the
+lookups of a block: 224 for AES-256, 87.77e9 blocks/s, Hirose; 160 for AES-128, 122.88e9, MMO).  Baselines in the same
 process on the same keys:
   loop       K single-key eval_range_device calls on the keys' single-key CWBs — what a caller had
-             before the multi-key entry point; at most 2^12 keys are looped and the time is scaled to K;
+             before the multi-key entry point; at most --loop-keys (2^12) keys are looped and the time is
+             scaled to K;
   pointwise  eval_multikey_device on the materialised points.
 
 Every figure is the median of REPS >= 10 repetitions timed one by one with HIP events after WARMUP
 untimed ones; min and max are kept beside it.  Prints one JSON document and writes it to --out
-(default profiles/range_multikey_bench.json).
+(default profiles/range_multikey_bench.json, range_multikey_bench_mmo.json with --prg mmo).
 
-  python scripts/range_multikey_bench.py [--out FILE] [--reps 10] [--warmup 3] [--shapes n1,n2,n16]
+  python scripts/range_multikey_bench.py [--prg hirose|mmo] [--out FILE] [--reps 10] [--warmup 3] [--shapes n1,n2,n16] [--loop-keys 4096]
+                                         [--max-keys K]
 """
 import argparse
 import json
@@ -30,8 +33,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import dcf_amd  # noqa: E402
 
-LDS_BOUND_BLOCKS_PER_S = 87.77e9  # VERDICT.md Weak #2
-LOOP_KEYS_MAX = 1 << 12
+LDS_LOOKUPS_PER_S = 256 * 32 * 2.4e9  # VERDICT.md Weak #2
+LDS_PER_BLOCK = {"hirose": 224, "mmo": 160}  # T-table lookups of an AES-256 / AES-128 block
 
 SHAPES = {  # name: (N, count or None for the whole domain, K)
     "n1": (1, None, 1 << 20),
@@ -83,22 +86,32 @@ def spread_apart(fast, slow):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "range_multikey_bench.json"))
+    ap.add_argument("--prg", choices=("hirose", "mmo"), default="hirose")
+    ap.add_argument("--out")
+    ap.add_argument("--loop-keys", type=int, default=1 << 12)
+    ap.add_argument("--max-keys", type=int, help="cap every shape's K (a library whose path runs key by key)")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--shapes", default="n1,n2,n16")
     a = ap.parse_args()
     assert a.reps >= 10, "median of at least 10 repetitions"
+    a.out = a.out or os.path.join("profiles", "range_multikey_bench.json" if a.prg == "hirose"
+                                  else f"range_multikey_bench_{a.prg}.json")
+    LDS_BOUND_BLOCKS_PER_S, LOOP_KEYS_MAX = LDS_LOOKUPS_PER_S / LDS_PER_BLOCK[a.prg], a.loop_keys
     lam = 16
     rng = np.random.default_rng(0x7B)
-    prg = dcf_amd.Aes256HirosePrg([rng.bytes(32) for _ in range(2)], lam)
-    res = {"device": torch.cuda.get_device_name(0), "library": dcf_amd.load().dcf_version().decode(),
+    if a.prg == "mmo":
+        prg = dcf_amd.Aes128MatyasMeyerOseasPrg([rng.bytes(16) for _ in range(4)], lam)
+    else:
+        prg = dcf_amd.Aes256HirosePrg([rng.bytes(32) for _ in range(2)], lam)
+    res = {"device": torch.cuda.get_device_name(0), "prg": a.prg, "library": dcf_amd.load().dcf_version().decode(),
            "lds_bound_blocks_per_s": LDS_BOUND_BLOCKS_PER_S, "loop_keys_max": LOOP_KEYS_MAX, "shapes": []}
     g = torch.Generator(device="cuda").manual_seed(0x7B)
     rnd = lambda *shape: torch.randint(0, 256, shape, dtype=torch.uint8, device="cuda", generator=g)  # noqa: E731
 
     for name in a.shapes.split(","):
         nb, count, K = SHAPES[name]
+        K = min(K, a.max_keys or K)
         d = dcf_amd.DcfImpl(nb, lam, prg)
         if count is None:
             x0, count = 0, 1 << (8 * nb)

@@ -36,6 +36,7 @@ EXPORTS = [
     "dcf_prg_device_bytes", "dcf_prg_host_pinned_bytes", "dcf_prg_workspaces", "dcf_prg_trim", "dcf_prg_set_phase_timing",
     "dcf_prg_last_eval_phases", "dcf_eval_range_device", "dcf_eval_range", "dcf_eval_range_subtree_levels",
     "dcf_eval_range_multikey_device", "dcf_eval_range_multikey_subtree_levels", "dcf_eval_range_keys_per_launch",
+    "dcf_eval_range_wide_points_per_launch",
 ]
 
 
@@ -90,6 +91,7 @@ def load(path: str = LIB_PATH):
         "dcf_eval_range_device": ([vp, sz, i, u8p, u8p, u8p, ctypes.c_uint64, u8p, vp], i),
         "dcf_eval_range": ([vp, sz, i, u8p, sz, u8p, u8p, ctypes.c_uint64, u8p, sz], i),
         "dcf_eval_range_subtree_levels": ([sz, ctypes.c_uint64], i),
+        "dcf_eval_range_wide_points_per_launch": ([sz, sz], ctypes.c_uint64),
         "dcf_eval_range_multikey_device": ([vp, sz, sz, i, u8p, u8p, u8p, ctypes.c_uint64, u8p, vp], i),
         "dcf_eval_range_multikey_subtree_levels": ([sz, sz, ctypes.c_uint64], i),
         "dcf_eval_range_keys_per_launch": ([sz, sz, ctypes.c_uint64], sz),

@@ -42,6 +42,7 @@
 #include "kernels_wide_stream.h"
 #include "kernels_range.h"
 #include "kernels_range_mmo.h"
+#include "kernels_range_wide.h"
 
 namespace {
 
@@ -2196,12 +2197,149 @@ static int range_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, con
   return DCF_OK;
 }
 
+// ---- range eval over the Hirose PRG at lambda >= 32 (kernels_range_wide.h; DESIGN.md "Range eval, λ ≥ 32") ----
+
+// Outputs per launch group: the t-vector buffer's bound, as eval_wide bounds its passes, and 2^28.
+static uint64_t range_wide_points(size_t nb) {
+  return std::min<uint64_t>(wide_chunk_points(t_words((uint32_t)(8 * nb))), kRangeLaunch);
+}
+
+uint64_t dcf_eval_range_wide_points_per_launch(size_t n_bytes, size_t lambda) {
+  return n_bytes && n_bytes <= 16 && lambda >= 32 ? range_wide_points(n_bytes) : 0;
+}
+
+// The one workspace allocation of a launch group of n outputs: [t-vectors, 64 B per output
+// (lambda > 32; + 256 B as eval_wide: a tail's clamped t loads run past the last row) | two
+// ping-pong buffers of the 80-byte nodes of the level above the register tail | the roots'
+// t-vector prefixes, 64 B each (lambda > 32) | kRangeCtrs work counters].  The paired-slot tail's
+// per-workgroup counters are a buffer of their own (Workspace::d_tctr), not part of this.
+struct RangeWideWs {
+  size_t tv, buf, pre, total;
+};
+static RangeWideWs range_wide_ws(uint64_t n, uint32_t h, size_t lam) {
+  RangeWideWs r;
+  const uint64_t maxroots = (n >> h) + 2;
+  r.tv = lam > 32 ? align256(n * kTWords * 4) + 256 : 0;
+  r.buf = h ? align256((maxroots * 80) << (h - kRangeWideTail)) : 0;
+  r.pre = h && lam > 32 ? align256(maxroots * kTWords * 4) : 0;
+  r.total = r.tv + 2 * r.buf + r.pre + kRangeCtrs * sizeof(uint32_t);
+  return r;
+}
+
+// One launch group: the n points from xa into ys.  The caller has sized the workspace
+// (range_wide_ws), built the CW digest and zeroed the block count.
+static int range_wide_group(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
+                            const RangeX xa, uint64_t n, uint32_t h, const RangeWideWs& ws, uint8_t* ys) {
+  hipStream_t st = L.st;
+  Workspace* w = L.w;
+  const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * nb);
+  const uint8_t* cwv = cwb + (size_t)nlev * lam;
+  const uint8_t* np1 = cwb + dcf_cwb_np1_offset(nb, lam, 1);
+  const uint4* dig = (const uint4*)w->d_dig;
+  const uint8_t* dig_t = w->d_dig + (size_t)nlev * 64;
+  unsigned long long* blocks = reinterpret_cast<unsigned long long*>(w->d_ctr) + 1;
+  uint32_t* tvec = lam > 32 ? reinterpret_cast<uint32_t*>(w->d_ws) : nullptr;
+  const uint64_t cus = (uint64_t)p->cus;
+  const bool mask = lam == 32;
+#define DCF_RW(K, grid, ...)                                                                              \
+  do {                                                                                                    \
+    if (mask) hipLaunchKernelGGL((K<true>), dim3((unsigned)(grid)), dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig, dig_t, __VA_ARGS__); \
+    else hipLaunchKernelGGL((K<false>), dim3((unsigned)(grid)), dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig, dig_t, __VA_ARGS__);     \
+    HIP_TRY(hipGetLastError());                                                                           \
+  } while (0)
+  if (h == 0) {  // every point is its own root: the root walk writes y[0:32) and the t-vector
+    if (mask) hipLaunchKernelGGL((k_range_roots_wide<true, true>), dim3((unsigned)std::min<uint64_t>(cus, (n + 63) / 64)), dim3(kBlock), 0, st,
+                                 p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, (const uint4*)s0, (uint32_t)party, xa, nlev,
+                                 (uint32_t)n, (uint4*)nullptr, tvec, ys, lam, blocks);
+    else hipLaunchKernelGGL((k_range_roots_wide<true, false>), dim3((unsigned)std::min<uint64_t>(cus, (n + 63) / 64)), dim3(kBlock), 0, st,
+                            p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, (const uint4*)s0, (uint32_t)party, xa, nlev,
+                            (uint32_t)n, (uint4*)nullptr, tvec, ys, lam, blocks);
+    HIP_TRY(hipGetLastError());
+  } else {
+    const uint32_t m = h - kRangeWideTail;  // breadth-first levels below a root
+    const uint32_t w0 = (nlev - h + 1) >> 4;  // the t-vector word of the first row below the roots
+    const uint64_t skip = xa.lo & ((1ull << h) - 1);
+    const RangeX pfx{(xa.lo >> h) | (xa.hi << (64 - h)), xa.hi >> h};
+    const uint64_t nroots = ((skip + n - 1) >> h) + 1;  // <= (n >> h) + 2
+    uint4* cur = (uint4*)(w->d_ws + ws.tv);
+    uint4* nxt = (uint4*)(w->d_ws + ws.tv + ws.buf);
+    uint32_t* tpre = lam > 32 ? (uint32_t*)(w->d_ws + ws.tv + 2 * ws.buf) : nullptr;
+    uint32_t* ctrs = (uint32_t*)(w->d_ws + ws.tv + 2 * ws.buf + ws.pre);
+    HIP_TRY(hipMemsetAsync(ctrs, 0, kRangeCtrs * sizeof(uint32_t), st));
+    if (mask) hipLaunchKernelGGL((k_range_roots_wide<false, true>), dim3((unsigned)std::min<uint64_t>(cus, (nroots + 63) / 64)), dim3(kBlock), 0,
+                                 st, p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, (const uint4*)s0, (uint32_t)party, pfx,
+                                 nlev - h, (uint32_t)nroots, cur, tpre, (uint8_t*)nullptr, lam, blocks);
+    else hipLaunchKernelGGL((k_range_roots_wide<false, false>), dim3((unsigned)std::min<uint64_t>(cus, (nroots + 63) / 64)), dim3(kBlock), 0,
+                            st, p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, (const uint4*)s0, (uint32_t)party, pfx,
+                            nlev - h, (uint32_t)nroots, cur, tpre, (uint8_t*)nullptr, lam, blocks);
+    HIP_TRY(hipGetLastError());
+    for (uint32_t k = 0; k < m; ++k) {  // level 8N - h + k: nroots << k parents
+      const uint64_t parents = nroots << k;
+      DCF_RW(k_range_level_wide, grid_for(parents, p->cus), nlev - h + k, w0, (uint32_t)parents, (const uint4*)cur, nxt,
+             ctrs + k, blocks);
+      std::swap(cur, nxt);
+    }
+    const uint64_t nnodes = nroots << m;
+    const uint32_t nq = ((nlev >> 4) + 1 + 3) / 4;  // uint4s holding rows 0 .. 8N of a t-vector
+    if (mask) hipLaunchKernelGGL((k_range_tail_wide<(int)kRangeWideTail, true>), dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock), 0, st,
+                                 p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, nlev - kRangeWideTail, w0, (uint32_t)nnodes,
+                                 (const uint4*)cur, (uint32_t)skip, (uint32_t)n, ys, lam, (uint4*)tvec, (const uint4*)tpre, m, nq,
+                                 ctrs + kRangeCtrs - 1, blocks);
+    else hipLaunchKernelGGL((k_range_tail_wide<(int)kRangeWideTail, false>), dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock), 0, st,
+                            p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, nlev - kRangeWideTail, w0, (uint32_t)nnodes,
+                            (const uint4*)cur, (uint32_t)skip, (uint32_t)n, ys, lam, (uint4*)tvec, (const uint4*)tpre, m, nq,
+                            ctrs + kRangeCtrs - 1, blocks);
+    HIP_TRY(hipGetLastError());
+  }
+#undef DCF_RW
+  if (lam > 32)  // y[32, lambda) from the t-vectors (the existing tail kernels)
+    return run_tail(cwb, cwv, np1, s0, nlev, lam, 1, 0, tvec, n, ys, st, p->cus, n, party, w);
+  return DCF_OK;
+}
+
+// Points [off, off + cnt) of the range into ys by the tree path above, on L.st: no materialised
+// points, no buffer of the call's own, no stream wait.
+static int range_wide_launch(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
+                             const RangeArg& A, uint64_t off, uint64_t cnt, uint32_t h, uint8_t* ys, bool zero_blocks) {
+  hipStream_t st = L.st;
+  Workspace* w = L.w;
+  const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * nb);
+  if (int rc = ensure_ctr(w)) return rc;
+  const uint64_t group = range_wide_points(nb);
+  const RangeWideWs ws = range_wide_ws(std::min<uint64_t>(cnt, group), h, lam);
+  if (int rc = ensure_ws(w, ws.total, st)) return rc;
+  if (w->dig_levels < nlev) {
+    size_t have = (size_t)w->dig_levels * 65;
+    if (int rc = grow(&w->d_dig, &have, (size_t)nlev * 65, st)) return rc;
+    w->dig_levels = nlev;
+  }
+  if (zero_blocks) HIP_TRY(hipMemsetAsync(w->d_ctr, 0, kCtrBytes, st));
+  w->last_prefix = 0;
+  phase_mark(p, L, 0);
+  // CW digest of the key, once per call: bytes [0,32) of each level's cw_s / cw_v, and cw_t
+  hipLaunchKernelGGL(k_cw_digest, dim3((4 * nlev + 255) / 256), dim3(256), 0, st, cwb, cwb + (size_t)nlev * lam,
+                     cwb + 2 * (size_t)nlev * lam, nlev, lam, (uint64_t)1, (uint64_t)0, 1u, (uint4*)w->d_dig,
+                     w->d_dig + (size_t)nlev * 64);
+  HIP_TRY(hipGetLastError());
+  phase_mark(p, L, 1);
+  for (uint64_t o = 0; o < cnt; o += group) {  // h = 0: cnt < 2^12, one group
+    const uint64_t n = std::min<uint64_t>(group, cnt - o);
+    if (int rc = range_wide_group(p, L, nb, party, cwb, s0, range_add(A.x, off + o), n, h, ws, ys + o * (uint64_t)lam))
+      return rc;
+  }
+  phase_mark(p, L, 2);
+  p->last_ws.store(w);
+  return DCF_OK;
+}
+
 // Points [off, off + cnt) of the range into ys (the output of point `off`), on L.st.  h: the
 // call's block height (range_levels of its whole count).  zero_blocks: first part of a call.
 static int range_launch(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
                         const RangeArg& A, uint64_t off, uint64_t cnt, uint32_t h, uint8_t* ys, bool zero_blocks) {
   hipStream_t st = L.st;
   const size_t lam = p->lambda;
+  if (p->kind == 0 && lam >= 32 && nb <= 16)
+    return range_wide_launch(p, L, nb, party, cwb, s0, A, off, cnt, h, ys, zero_blocks);
   if (lam != 16 || nb > 16) {  // no tree-sharing path: materialise the points, run eval
     DevBuf xs;  // eval owns the workspace, so the points get their own buffer
     const uint64_t chunk = std::min<uint64_t>(cnt, kRangeChunk);

@@ -20,9 +20,11 @@
 //                     leaf's output index is its distance from x0 and leaves outside the range are
 //                     not stored.
 // Each is a template on the key policy, RangeOneKey or RangeKeys, and is instantiated for both.
-// kernels_range_mmo.h has the three stages over the MMO PRG, on the same key policies.
-//   k_range_points    the points x0 + i as N-byte big-endian strings, for LAMBDA >= 32 and N > 16,
-//                     which have no tree-sharing path (the existing eval runs on them).
+// kernels_range_mmo.h has the three stages over the MMO PRG, on the same key policies;
+// kernels_range_wide.h has them over the Hirose PRG's head state at LAMBDA >= 32, for one key.
+//   k_range_points    the points x0 + i as N-byte big-endian strings, for the MMO PRG at
+//                     LAMBDA >= 32 and for N > 16, which have no tree-sharing path (the existing
+//                     eval runs on them).
 //   k_rangemk_gather  key k of a K-key block as a single-key block (the same slow path, key by key).
 // The pointers the kernels get are already advanced to the first key of the launch group; K stays
 // the row stride.  All node, key and output indices of a tree launch are 32-bit (the host keeps

@@ -405,11 +405,19 @@ class DcfImpl:
         (dcf_eval_range_subtree_levels; the rule is in include/dcf_hip.h)."""
         return int(_lib.load().dcf_eval_range_subtree_levels(self.n_bytes, int(count)))
 
+    def range_wide_points_per_launch(self) -> int:
+        """Outputs per launch group of the Hirose LAMBDA >= 32 tree path of eval_range
+        (dcf_eval_range_wide_points_per_launch); 0 for a shape that path does not take."""
+        return int(_lib.load().dcf_eval_range_wide_points_per_launch(self.n_bytes, self.lam))
+
     def eval_range_device(self, b: bool, cwb, s0, x0, count: int, ys=None):
         """`Dcf::eval` at x0 + i for i in [0, count) (x0: int or N big-endian bytes): the rows
         eval_device returns over those points, as a (count, LAMBDA) device tensor.
         LAMBDA = 16, N <= 16: tree expansion, 2 AES-256 blocks per output with the Hirose PRG, 4 AES-128
-        blocks with the MMO PRG; asynchronous on the current stream for both."""
+        blocks with the MMO PRG.  Hirose PRG, LAMBDA >= 32, N <= 16: tree expansion of bytes [0, 32), 4
+        AES-256 blocks per output, and the linear tail for bytes [32, LAMBDA) from the leaves'
+        t-vectors.  All three are asynchronous on the current stream; other shapes materialise the
+        points and wait for the stream."""
         import torch
         lam, nb, dev = self.lam, self.n_bytes, self.prg.device
         xb = self._x0(x0)
@@ -438,7 +446,9 @@ class DcfImpl:
         """K keys over one range: `Dcf::eval` of key k at x0 + i for i in [0, count), as a
         (K, count, LAMBDA) device tensor.  cwb: the K-key block of gen_batch_device, s0s (K, LAMBDA).
         LAMBDA = 16, N <= 16: one tree expansion over all keys, 2 AES-256 blocks per output with the
-        Hirose PRG, 4 AES-128 blocks with the MMO PRG; asynchronous on the current stream for both."""
+        Hirose PRG, 4 AES-128 blocks with the MMO PRG; asynchronous on the current stream for both.
+        LAMBDA >= 32 goes key by key through eval_range_device's path (the Hirose tree expansion at
+        N <= 16) and waits for the stream."""
         import torch
         lam, nb, dev = self.lam, self.n_bytes, self.prg.device
         xb = self._x0(x0)
@@ -457,7 +467,8 @@ class DcfImpl:
 
     def eval_range(self, b: bool, k: Share, x0, count: int, ys=None):
         """Host buffers (dcf_eval_range): ys is a (count, LAMBDA) uint8 numpy array, overwritten in
-        place when given.  Returns ys."""
+        place when given.  Returns ys.  The chunks run eval_range_device's path for the shape (tree
+        expansion at LAMBDA = 16 and, with the Hirose PRG, at LAMBDA >= 32, N <= 16)."""
         lam, nb = self.lam, self.n_bytes
         cwb = share_to_cwb(k, nb, lam)
         xb = self._x0(x0)

@@ -241,6 +241,8 @@ class DcfImpl final : public Dcf<N, LAMBDA> {
 
   // Height of the aligned blocks eval_range expands for `count` points.
   static int range_subtree_levels(uint64_t count) { return dcf_eval_range_subtree_levels(N, count); }
+  // Outputs per launch group of the Hirose LAMBDA >= 32 tree path of eval_range (0: not that path).
+  static uint64_t range_wide_points_per_launch() { return dcf_eval_range_wide_points_per_launch(N, LAMBDA); }
 
   // num_keys keys over one range, device form (dcf_eval_range_multikey_device): row k * count + i
   // of ys is Dcf::eval(b, key k, x0 + i).  cwb: the K-key CWB of dcf_gen_batch_device, s0s:

@@ -318,8 +318,28 @@ int dcf_eval_full_domain_device(dcf_prg* prg, size_t n_bytes, int party, const u
  *   path: no materialised points, no stream wait.  dcf_prg_last_eval_blocks then reports the
  *   executed AES-128 blocks: nroots (2 (8N - h) + 4 (2^h - 1)) per launch, clipped leaves
  *   included, and 2 * 8N * count at h = 0.
- *   Otherwise (lambda >= 32, N > 16) the points are materialised on the device, 2^22 at a
- *   time, and dcf_eval_device's path runs on them; that path waits for the stream before returning.
+ *   Hirose PRG, lambda >= 32, N <= 16 (kernels_range_wide.h): the same blocks and heights over the
+ *   head state of that PRG — only bytes [0,32) of a node see AES, under ciphers 0 and 17, and a
+ *   node's two children cost the four blocks A, B, C, D of kernels_wide.h.  The roots are walked one
+ *   lane each (all four blocks per level), the levels below are expanded breadth-first, one launch
+ *   each, on 80-byte rows, and the last 3 levels depth-first in registers (a wide node is 19
+ *   words): 4 AES-256 blocks per output instead of 2.5 * 8N per point.  The tail writes y[0:32) of
+ *   every leaf inside the range and, when lambda > 32, the leaf's t-vector (its root's prefix plus
+ *   the subtree's bits), from which the existing tail kernels write y[32, lambda).  h = 0
+ *   (count < 2^12): the root walk is the point walk and writes y[0:32) and the t-vector itself.
+ *   A call runs as consecutive launch groups of dcf_eval_range_wide_points_per_launch outputs
+ *   (32-bit indices within a group, 64-bit offsets across them).  One workspace allocation holds a
+ *   group's t-vectors (64 B per output, lambda > 32), the two node buffers (80 B per node of the
+ *   level three above the leaves), the roots' t-vector prefixes and the work counters; the CW
+ *   digest is built once per call.  Asynchronous on `stream` like the lambda = 16 paths: no
+ *   materialised points, no buffer of the call's own, no stream wait.  dcf_prg_last_eval_blocks
+ *   then reports the executed AES-256 blocks of roots, levels and tail, clipped leaves included:
+ *     sum over groups of nroots * (4 (8N - h) + 4 (2^h - 1)),
+ *     nroots = (((x mod 2^h) + n - 1) >> h) + 1 for a group of n outputs from x,
+ *   and 4 * 8N * count at h = 0.
+ *   Otherwise (the MMO PRG at lambda >= 32, N > 16) the points are materialised on the device,
+ *   2^22 at a time, and dcf_eval_device's path runs on them; that path waits for the stream
+ *   before returning.
  * Errors, nothing launched: x0 + count > 2^(8N) -> DCF_ERR_ARG; bad party / null pointer ->
  * DCF_ERR_ARG; n_bytes == 0 -> DCF_ERR_N; N > 256 -> DCF_ERR_UNSUPPORTED.  count == 0 -> DCF_OK,
  * nothing written. */
@@ -341,6 +361,12 @@ int dcf_eval_range(dcf_prg* prg, size_t n_bytes, int party, const uint8_t* cwb, 
  * above a 4-level register tail.  Root paths cost 2 (8N - h) / 2^h AES blocks per output (< 0.94 at N = 16), the two
  * clipped edge blocks at most 4 * 2^h blocks in all. */
 int dcf_eval_range_subtree_levels(size_t n_bytes, uint64_t count);
+
+/* Outputs per launch group of the Hirose lambda >= 32 tree path of dcf_eval_range* (pure
+ * arithmetic, no device access): the points whose t-vectors fill the 256 MiB the point walk's
+ * passes use (2^22 at N <= 16), and at most 2^28.  0 for a shape that path does not take
+ * (n_bytes == 0, n_bytes > 16, lambda < 32). */
+uint64_t dcf_eval_range_wide_points_per_launch(size_t n_bytes, size_t lambda);
 
 /* Multi-key contiguous-range eval: K keys over one range, ys[(k * count + i) * lambda ..] =
  * Dcf::eval(party, key k, x0 + i) — dcf_eval_range_device of every key of a K-key block in one
@@ -368,8 +394,10 @@ int dcf_eval_range_subtree_levels(size_t n_bytes, uint64_t count);
  *   (key, point) pairs.  Asynchronous on `stream` like the Hirose path: no key-by-key gather, no
  *   stream wait.  dcf_prg_last_eval_blocks then reports the executed AES-128 blocks,
  *   keys * nroots (2 (8N - h) + 4 (2^h - 1)) per group, and 2 * 8N * K * count at h = 0.
- *   Otherwise (lambda >= 32, N > 16) — the slow path: key by key, each gathered into the
- *   single-key layout and run through dcf_eval_range_device's path; it waits for the stream.
+ *   Otherwise (lambda >= 32, N > 16) — key by key: each key is gathered into the single-key
+ *   layout in a buffer of the call's own and run through dcf_eval_range_device's path, so the
+ *   Hirose PRG at lambda >= 32, N <= 16 gets that path's tree expansion for every key; the call
+ *   still goes key by key and still waits for the stream before it returns.
  * Errors, nothing launched: null prg / cwb / s0s / x0, null ys with work to do, bad party ->
  * DCF_ERR_ARG; n_bytes == 0 -> DCF_ERR_N; N > 256 -> DCF_ERR_UNSUPPORTED; x0 + count > 2^(8N) ->
  * DCF_ERR_ARG.  num_keys == 0 or count == 0 -> DCF_OK, nothing written. */

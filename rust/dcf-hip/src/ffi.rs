@@ -76,6 +76,7 @@ extern "C" {
     pub fn dcf_eval_range(prg: *mut DcfPrg, n_bytes: usize, party: c_int, cwb: *const u8, cwb_len: usize,
                           s0: *const u8, x0: *const u8, count: u64, ys: *mut u8, ys_len: usize) -> c_int;
     pub fn dcf_eval_range_subtree_levels(n_bytes: usize, count: u64) -> c_int;
+    pub fn dcf_eval_range_wide_points_per_launch(n_bytes: usize, lambda: usize) -> u64;
     pub fn dcf_eval_range_multikey_device(prg: *mut DcfPrg, n_bytes: usize, num_keys: usize, party: c_int,
                                           cwb: *const u8, s0s: *const u8, x0: *const u8, count: u64, ys: *mut u8,
                                           stream: *mut c_void) -> c_int;

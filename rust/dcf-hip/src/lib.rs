@@ -156,6 +156,12 @@ impl<const N: usize, const LAMBDA: usize> DcfHip<N, LAMBDA> {
         unsafe { ffi::dcf_eval_range_subtree_levels(N, count) }
     }
 
+    /// Outputs per launch group of the Hirose `LAMBDA >= 32` tree path of `eval_range`
+    /// (`dcf_eval_range_wide_points_per_launch`); 0 for a shape that path does not take.
+    pub fn range_wide_points_per_launch() -> u64 {
+        unsafe { ffi::dcf_eval_range_wide_points_per_launch(N, LAMBDA) }
+    }
+
     /// `num_keys` keys over one range, device buffers (`dcf_eval_range_multikey_device`): row
     /// `k * count + i` of `ys` is `Dcf::eval(b, key k, x0 + i)`.  `cwb` is the K-key block of
     /// `dcf_gen_batch_device`, `s0s` `num_keys * LAMBDA` bytes, `ys` `num_keys * count * LAMBDA`

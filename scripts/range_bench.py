@@ -1,4 +1,5 @@
-"""Contiguous-range eval (dcf_eval_range_device) on one MI355X, Hirose or MMO PRG (--prg), LAMBDA = 16.
+"""Contiguous-range eval (dcf_eval_range_device) on one MI355X, Hirose or MMO PRG (--prg), LAMBDA = 16
+or --lam (the Hirose PRG at LAMBDA >= 32 takes 18 keys; blocks are then the AES-256 blocks of bytes [0, 32)).
 
   (a) N = 16, count = 2^16, 2^20, 2^24, 2^28 at a random unaligned x0: outputs/s and AES blocks
       per output (dcf_prg_last_eval_blocks, counted on the device);
@@ -12,7 +13,11 @@ Every figure is the median of REPS >= 10 repetitions timed one by one with HIP e
 WARMUP untimed ones; min and max are kept beside it.  Prints one JSON document and writes it to
 --out (default profiles/range_bench.json, range_bench_mmo.json with --prg mmo).
 
-  python scripts/range_bench.py [--prg hirose|mmo] [--out FILE] [--reps 10] [--warmup 3] [--skip-full-domain]
+  python scripts/range_bench.py [--prg hirose|mmo] [--lam 16] [--log2-counts 16,20,24,28] [--out FILE]
+                                [--reps 10] [--warmup 3] [--skip-full-domain] [--skip-pointwise]
+
+--skip-pointwise leaves (b) out (at LAMBDA = 16384 and 2^22 points its outputs are a second 64 GiB);
+every range row carries a checksum of its outputs, so two libraries can be compared run to run.
 """
 import argparse
 import json
@@ -74,42 +79,48 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--skip-full-domain", action="store_true")
+    ap.add_argument("--skip-pointwise", action="store_true")
+    ap.add_argument("--lam", type=int, default=16)
+    ap.add_argument("--log2-counts", default="16,20,24,28")
     a = ap.parse_args()
     assert a.reps >= 10, "median of at least 10 repetitions"
     a.out = a.out or os.path.join("profiles", "range_bench.json" if a.prg == "hirose" else f"range_bench_{a.prg}.json")
     LDS_BOUND_BLOCKS_PER_S = LDS_LOOKUPS_PER_S / LDS_PER_BLOCK[a.prg]
-    lam = 16
+    lam = a.lam
     rng = np.random.default_rng(0x7A)
     if a.prg == "mmo":
-        prg = dcf_amd.Aes128MatyasMeyerOseasPrg([rng.bytes(16) for _ in range(4)], lam)
+        prg = dcf_amd.Aes128MatyasMeyerOseasPrg([rng.bytes(16) for _ in range(4 * lam // 16)], lam)
     else:
-        prg = dcf_amd.Aes256HirosePrg([rng.bytes(32) for _ in range(2)], lam)
-    res = {"device": torch.cuda.get_device_name(0), "prg": a.prg, "library": dcf_amd.load().dcf_version().decode(),
+        prg = dcf_amd.Aes256HirosePrg([rng.bytes(32) for _ in range(2 if lam == 16 else 18)], lam)
+    res = {"device": torch.cuda.get_device_name(0), "prg": a.prg, "lambda": lam,
+           "library": dcf_amd.load().dcf_version().decode(),
            "lds_bound_blocks_per_s": LDS_BOUND_BLOCKS_PER_S, "ranges": []}
 
     nb = 16
     d = dcf_amd.DcfImpl(nb, lam, prg)
     x0 = (int.from_bytes(rng.bytes(8), "big") << 64) | (int.from_bytes(rng.bytes(7), "big") | 1)
-    for e in (16, 20, 24, 28):
+    for e in (int(v) for v in a.log2_counts.split(",")):
         count = 1 << e
         cwb, s0 = key(d, nb, lam, rng, x0 + count // 3)
         ys = torch.empty((count, lam), dtype=torch.uint8, device="cuda")
         t = timed(lambda: d.eval_range_device(False, cwb, s0, x0, count, ys), a.reps, a.warmup)
         blocks = prg.last_eval_blocks()
-        xs = points(x0, count, nb)
-        yp = torch.empty((count, lam), dtype=torch.uint8, device="cuda")
-        tp = timed(lambda: d.eval_device(False, cwb, s0, xs, yp), a.reps, a.warmup)
-        equal = bool(torch.equal(ys, yp))
         row = {"n_bytes": nb, "count": count, "subtree_levels": d.range_subtree_levels(count),
                "range": t, "range_outputs_per_s": count / (t["median_ms"] * 1e-3),
                "blocks": blocks, "blocks_per_output": blocks / count,
                "blocks_per_s": blocks / (t["median_ms"] * 1e-3),
                "lds_bound_frac": blocks / (t["median_ms"] * 1e-3) / LDS_BOUND_BLOCKS_PER_S,
-               "pointwise": tp, "pointwise_evals_per_s": count / (tp["median_ms"] * 1e-3),
-               "speedup": tp["median_ms"] / t["median_ms"], "outputs_equal": equal}
+               "ys_checksum": int(ys.view(torch.int64).sum().item())}
+        if not a.skip_pointwise:
+            xs = points(x0, count, nb)
+            yp = torch.empty((count, lam), dtype=torch.uint8, device="cuda")
+            tp = timed(lambda: d.eval_device(False, cwb, s0, xs, yp), a.reps, a.warmup)
+            row.update({"pointwise": tp, "pointwise_evals_per_s": count / (tp["median_ms"] * 1e-3),
+                        "speedup": tp["median_ms"] / t["median_ms"], "outputs_equal": bool(torch.equal(ys, yp))})
+            del xs, yp
         res["ranges"].append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
-        del xs, yp, ys
+        del ys
         torch.cuda.empty_cache()
 
     if not a.skip_full_domain:

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests.test_range_multikey_gpu import _nroots
 
 pytestmark = pytest.mark.gpu
 
@@ -202,11 +203,17 @@ def test_errors(dcf, hip_lib):
     assert not hy.any()
 
 
-def test_fallback_mmo(dcf):
+# ---- the other tree paths at h = 0 (written for the materialising path, which these shapes have
+# since left; that path is covered by tests/test_range_points_gpu.py) ----
+
+def test_mmo_direct_walk(dcf):
+    """MMO PRG, LAMBDA = 16, N = 4, 3001 points: below 2^12, so k_range_roots16_mmo walks every point."""
     run_range(dcf, 4, 0x00FFF123, 3001, 900, bounds=(0, 1), kind="mmo")
 
 
-def test_fallback_hirose_lambda_32(dcf):
+def test_hirose_lambda_32_direct_walk(dcf):
+    """Hirose PRG, LAMBDA = 32, N = 2, 777 points: leaf mode of the LAMBDA >= 32 tree path
+    (k_range_roots_wide writes y)."""
     run_range(dcf, 2, 0x01F0, 777, 901, bounds=(0, 1), lam=32)  # crosses 0x01FF -> 0x0200 and two more byte carries
 
 
@@ -228,3 +235,64 @@ def test_host_entry_point(dcf):
         ys.append(y)
     rec = ys[0] ^ ys[1]
     assert (rec[:off] == np.frombuffer(beta, np.uint8)).all() and not rec[off:].any()
+
+
+def host_chunk(lam):
+    """Outputs per chunk of dcf_eval_range: include/dcf_hip.h, "outputs come back in chunks of up to
+    128 MiB through the prg's staging pool" (at least 256 outputs)."""
+    return max(256, (128 << 20) // lam)
+
+
+def run_host_chunked(dcf, kind, lam, nb, x0, count, seed, walk, node, parties=(1,), bound=0, alpha_off=None, group=1 << 28):
+    """dcf_eval_range over more than one chunk.  Every chunk after the first starts where the one
+    before ended, mid-block, at the height h of the whole count; the last may be a few points.
+    Per party: the host result against eval_range_device over the same range (all rows, on the
+    device), against the oracle on _sample rows and 2048 rows on each side of the chunk boundary,
+    and the call's block count: at least 2 per output and at most the sum over the chunks (and
+    the launch groups of `group` outputs inside a chunk) of the documented bound of a launch,
+    nroots (walk (8N - h) + node (2^h - 1)) — so the count is neither reset nor doubled between
+    chunks.  Both parties given: reconstruction on all rows."""
+    import torch
+    chunk = host_chunk(lam)
+    assert chunk < count
+    rng = np.random.default_rng(seed)
+    prg, P = _prgs(dcf, kind, lam, rng)
+    d = dcf.DcfImpl(nb, lam, prg)
+    h = d.range_subtree_levels(count)
+    assert h > 0
+    off = int(rng.integers(0, count)) if alpha_off is None else alpha_off
+    alpha, beta, seeds = (x0 + off).to_bytes(nb, "big"), rng.bytes(lam), [rng.bytes(lam), rng.bytes(lam)]
+    ok = O.gen(P, alpha, beta, seeds[0], seeds[1], bound)
+    cwb = _dev(_cwb(ok))
+    idx = np.unique(np.concatenate([_sample(count, rng), np.arange(chunk - 2048, min(chunk + 2048, count))]))
+    xs = _points(nb, x0, idx)
+    launches = [(x0 + o + g, min(group, n - g)) for o in range(0, count, chunk)
+                for n in [min(chunk, count - o)] for g in range(0, n, group)]
+    upper = sum(_nroots(x, n, h) * (walk * (8 * nb - h) + node * ((1 << h) - 1)) for x, n in launches)
+    ys = []
+    for b in parties:
+        y = d.eval_range(bool(b), dcf.cwb_to_share(_cwb(ok), nb, lam, [seeds[b]]), x0, count)
+        blocks = prg.last_eval_blocks()
+        print(f"{kind} lam={lam} N={nb} count={count} h={h}: {len(launches)} launches, {blocks} blocks, bound {upper}")
+        assert 2 * count <= blocks <= upper, (blocks, 2 * count, upper)
+        yh = torch.from_numpy(y).cuda()
+        ydev = d.eval_range_device(bool(b), cwb, _dev(seeds[b]), x0, count)
+        torch.cuda.synchronize()
+        assert torch.equal(yh, ydev), ("host and device entry points differ", b)
+        want = O.eval_(P, b, ok, seeds[b], xs, nthreads=8)
+        bad = np.flatnonzero((y[idx] != want).any(axis=1))
+        assert bad.size == 0, (kind, lam, nb, hex(x0), count, b, "first mismatching i", idx[bad[:8]])
+        ys.append(yh)
+        del ydev, y
+    if len(ys) == 2:
+        rec = ys[0] ^ ys[1]
+        lo, hi = (rec[:off], rec[off:]) if bound == 0 else (rec[off + 1:], rec[:off + 1])
+        assert bool((lo == _dev(beta)).all()) and not bool(hi.any()), ("reconstruction", kind, lam, nb, count)
+
+
+def test_host_entry_point_chunked(dcf):
+    """Hirose, LAMBDA = 16, N = 16, odd x0, one chunk and 3 points: h = 14, and the last chunk is 3
+    points at h = 14 (a shape the device entry point has only at h = 0); alpha in that chunk."""
+    count = host_chunk(16) + 3
+    x0 = (int.from_bytes(np.random.default_rng(1001).bytes(16), "big") >> 1) | 1
+    run_host_chunked(dcf, "hirose", 16, 16, x0, count, 1001, walk=2, node=2, parties=(0, 1), alpha_off=count - 2)

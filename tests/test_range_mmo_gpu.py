@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from tests.test_range_gpu import PAD, SENTINEL, _cwb, _dev, _points, _sample
+from tests.test_range_gpu import PAD, SENTINEL, _cwb, _dev, _points, _sample, host_chunk, run_host_chunked
 from tests.test_range_multikey_gpu import _alpha, _cwbk, _nroots
 
 pytestmark = pytest.mark.gpu
@@ -201,6 +201,12 @@ def test_host_entry_point(dcf):
         ys.append(y)
     rec = ys[0] ^ ys[1]
     assert (rec[:off] == np.frombuffer(beta, np.uint8)).all() and not rec[off:].any()
+
+
+def test_host_entry_point_chunked(dcf):
+    """One chunk of 2^23 outputs and 3 points from an odd x0: the last chunk is 3 points at h = 14.
+    One party."""
+    run_host_chunked(dcf, "mmo", LAM, 16, _odd_x0(2071), host_chunk(LAM) + 3, 2071, walk=2, node=4, bound=1)
 
 
 # ---- K keys ----

@@ -270,13 +270,17 @@ def test_one_key_larger_than_a_launch(dcf):
         assert torch.equal(y[k], single), k
 
 
-# ---- slow path ----
+# ---- the other PRG shapes (written for the key-by-key materialising path, which these shapes have
+# since left; that path is covered by tests/test_range_points_gpu.py) ----
 
-def test_fallback_mmo(dcf):
+def test_mmo_tree_path_three_keys(dcf):
+    """MMO PRG, LAMBDA = 16, N = 4, 3 keys x 3001 points: the MMO kernels of the K-key tree path, h = 9."""
     run_mk(dcf, 4, 0x00FFF123, 3001, 3, 1700, kind="mmo")
 
 
-def test_fallback_hirose_lambda_32(dcf):
+def test_hirose_lambda_32_key_by_key(dcf):
+    """Hirose PRG, LAMBDA = 32, N = 2, 2 keys x 777 points: k_rangemk_gather, then each key through
+    the single-key LAMBDA >= 32 tree path in leaf mode (h = 0)."""
     run_mk(dcf, 2, 0x01F0, 777, 2, 1701, lam=32)
 
 

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from tests.test_range_gpu import PAD, SENTINEL, _cwb, _dev, _points, _prgs, _sample
+from tests.test_range_gpu import PAD, SENTINEL, _cwb, _dev, _points, _prgs, _sample, host_chunk, run_host_chunked
 from tests.test_range_multikey_gpu import _cwbk, _nroots
 
 pytestmark = pytest.mark.gpu
@@ -176,6 +176,18 @@ def test_host_entry_point(dcf):
         ys.append(y)
     rec = ys[0] ^ ys[1]
     assert (rec[:off] == np.frombuffer(beta, np.uint8)).all() and not rec[off:].any()
+
+
+@pytest.mark.parametrize("extra", [4099, 5])
+def test_host_entry_point_chunked(dcf, extra):
+    """LAMBDA = 48, N = 4: a chunk is 2 796 202 outputs, no multiple of a block of 2^13, so the second
+    chunk (4099 or 5 points) starts mid-block; each chunk is one launch group.  One party."""
+    nb, lam = 4, 48
+    count = host_chunk(lam) + extra
+    assert host_chunk(lam) == 2796202
+    per = dcf.DcfImpl(nb, lam, _prgs(dcf, "hirose", lam, np.random.default_rng(3))[0]).range_wide_points_per_launch()
+    assert per >= host_chunk(lam)
+    run_host_chunked(dcf, "hirose", lam, nb, 0x0123457, count, 3500 + extra, walk=4, node=4, bound=extra % 2, group=per)
 
 
 def test_multikey_equals_single_key_calls(dcf):

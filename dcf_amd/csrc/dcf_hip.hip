@@ -2129,20 +2129,44 @@ static size_t range_ws_bytes(uint64_t keys, uint64_t n, uint32_t h, size_t* buf_
   return h ? 2 * *buf_bytes + kRangeCtrs * sizeof(uint32_t) : 0;
 }
 
-// A launch of the tree path's kernel for the prg's PRG: kh (Hirose, round keys by value) or km
-// (MMO, the AES-128 schedules on the device); both take the T-tables first and `a` after the keys.
-extern "C++" template <class KH, class KM, class... A>
-static void range_run(const dcf_prg* p, hipStream_t st, KH kh, KM km, uint64_t grid, A... a) {
-  if (p->kind == 0) hipLaunchKernelGGL(kh, dim3((unsigned)grid), dim3(kBlock), 0, st, p->d_tab, p->rk[0], a...);
-  else hipLaunchKernelGGL(km, dim3((unsigned)grid), dim3(kBlock), 0, st, p->d_tab, (const uint4*)p->d_rk128, a...);
+// The blocks of 2^h leaves (h >= 1) that cover the n points from xa: the range starts `skip` leaves
+// into the first, whose root has the (8N - h)-bit prefix pfx; nroots <= (n >> h) + 2 of them, with
+// m breadth-first levels between a root and the `tail` levels of the register tail.
+struct RangeGeom {
+  uint64_t skip, nroots;
+  RangeX pfx;
+  uint32_t m;
+};
+static RangeGeom range_geom(const RangeX xa, uint64_t n, uint32_t h, uint32_t tail) {
+  const uint64_t skip = xa.lo & ((1ull << h) - 1);
+  return {skip, ((skip + n - 1) >> h) + 1, RangeX{(xa.lo >> h) | (xa.hi << (64 - h)), xa.hi >> h}, h - tail};
 }
 
-// One launch group of the tree path (Hirose or MMO, lambda = 16, N <= 16): keys [key0, key0 + keys)
-// of a K-key block over the n <= 2^28 points from xa, keys * n <= 2^28; the outputs of key key0 + k
-// go to rows [k * n, (k + 1) * n) of ys (several keys in a group: n is the call's count).  KP: the
-// kernels' key policy — RangeOneKey takes key0 = 0, keys = K = 1.  The caller has sized the
-// workspace (range_ws_bytes) and zeroed the block count.
-extern "C++" template <class KP>
+// What a tree-path call does ahead of its launch groups and after them: the workspace of ws_bytes
+// (0: none), the block count zeroed (zero_blocks: first part of a call), phase mark 0 — the caller
+// sets mark 1 after what it builds once per call — and mark 2 at the end.
+static int range_begin(dcf_prg* p, Lease& L, size_t ws_bytes, bool zero_blocks) {
+  Workspace* w = L.w;
+  if (int rc = ensure_ctr(w)) return rc;
+  if (ws_bytes)
+    if (int rc = ensure_ws(w, ws_bytes, L.st)) return rc;
+  if (zero_blocks) HIP_TRY(hipMemsetAsync(w->d_ctr, 0, kCtrBytes, L.st));
+  w->last_prefix = 0;
+  phase_mark(p, L, 0);
+  return DCF_OK;
+}
+static int range_end(dcf_prg* p, Lease& L) {
+  phase_mark(p, L, 2);
+  p->last_ws.store(L.w);
+  return DCF_OK;
+}
+
+// One launch group of the tree path (lambda = 16, N <= 16): keys [key0, key0 + keys) of a K-key
+// block over the n <= 2^28 points from xa, keys * n <= 2^28; the outputs of key key0 + k go to rows
+// [k * n, (k + 1) * n) of ys (several keys in a group: n is the call's count).  PRG: the prg's PRG
+// policy, RangeHirose or RangeMmo.  KP: the kernels' key policy — RangeOneKey takes key0 = 0,
+// keys = K = 1.  The caller has sized the workspace (range_ws_bytes) and zeroed the block count.
+extern "C++" template <class PRG, class KP>
 static int range_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb, const uint8_t* s0s,
                        uint64_t key0, uint64_t keys, const RangeX xa, uint64_t n, uint32_t h, size_t buf_bytes,
                        uint8_t* ys) {
@@ -2157,42 +2181,40 @@ static int range_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, con
   const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(nb, lam, K)) + key0;
   const uint4* s0 = (const uint4*)s0s + key0;
   unsigned long long* blocks = reinterpret_cast<unsigned long long*>(w->d_ctr) + 1;
-  const uint64_t cus = (uint64_t)p->cus;
-  // roots per workgroup before a second one pays: a pass of half-waves (RowPrg), or one wave of lanes (MMO)
-  const uint64_t rper = p->kind == 0 ? kBlock / 32 : 64;
+  const typename PRG::Arg rk = PRG::arg(p);
+  const auto roots_grid = [&](uint64_t total) {
+    return dim3((unsigned)std::min<uint64_t>((uint64_t)p->cus, (total + PRG::kRootsPer - 1) / PRG::kRootsPer));
+  };
   if (h == 0) {  // every point is its own root: the root walk writes y
     const uint64_t total = keys * n;
-    range_run(p, st, k_range_roots16<true, KP>, k_range_roots16_mmo<true, KP>,
-              std::min<uint64_t>(cus, (total + rper - 1) / rper), cws, cwv, cwt, np1, s0,
-              KP::make(K, (uint32_t)n), (uint32_t)party, xa, nlev, (Idx)total, (uint4*)ys, blocks);
+    hipLaunchKernelGGL((PRG::template roots<true, KP>()), roots_grid(total), dim3(kBlock), 0, st, p->d_tab, rk, cws, cwv,
+                       cwt, np1, s0, KP::make(K, (uint32_t)n), (uint32_t)party, xa, nlev, (Idx)total, (uint4*)ys, blocks);
     HIP_TRY(hipGetLastError());
     return DCF_OK;
   }
-  const uint32_t m = h - kFdTail;  // breadth-first levels below a root
-  const uint64_t skip = xa.lo & ((1ull << h) - 1);
-  const RangeX pfx{(xa.lo >> h) | (xa.hi << (64 - h)), xa.hi >> h};
-  const uint64_t nroots = ((skip + n - 1) >> h) + 1;  // <= (n >> h) + 2
+  const RangeGeom g = range_geom(xa, n, h, kFdTail);
   uint32_t* ctrs = (uint32_t*)(w->d_ws + 2 * buf_bytes);
   uint4* cur = (uint4*)w->d_ws;
   uint4* nxt = (uint4*)(w->d_ws + buf_bytes);
   HIP_TRY(hipMemsetAsync(ctrs, 0, kRangeCtrs * sizeof(uint32_t), st));
-  const uint64_t total = keys * nroots;
-  range_run(p, st, k_range_roots16<false, KP>, k_range_roots16_mmo<false, KP>,
-            std::min<uint64_t>(cus, (total + rper - 1) / rper), cws, cwv, cwt, np1, s0,
-            KP::make(K, (uint32_t)nroots), (uint32_t)party, pfx, nlev - h, (Idx)total, cur, blocks);
+  const uint64_t total = keys * g.nroots;
+  hipLaunchKernelGGL((PRG::template roots<false, KP>()), roots_grid(total), dim3(kBlock), 0, st, p->d_tab, rk, cws, cwv,
+                     cwt, np1, s0, KP::make(K, (uint32_t)g.nroots), (uint32_t)party, g.pfx, nlev - h, (Idx)total, cur,
+                     blocks);
   HIP_TRY(hipGetLastError());
-  for (uint32_t k = 0; k < m; ++k) {  // level 8N - h + k: nroots << k parents per key
+  for (uint32_t k = 0; k < g.m; ++k) {  // level 8N - h + k: nroots << k parents per key
     const uint64_t parents = total << k;
-    range_run(p, st, k_range_level16<KP>, k_range_level16_mmo<KP>, grid_for(parents, p->cus), cws, cwv, cwt,
-              KP::make(K, (uint32_t)(nroots << k)), nlev - h + k, (uint32_t)parents, (const uint4*)cur, nxt, ctrs + k,
-              blocks);
+    hipLaunchKernelGGL((k_range_level16<PRG, KP>), dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st,
+                       p->d_tab, rk, cws, cwv, cwt, KP::make(K, (uint32_t)(g.nroots << k)), nlev - h + k,
+                       (uint32_t)parents, (const uint4*)cur, nxt, ctrs + k, blocks);
     HIP_TRY(hipGetLastError());
     std::swap(cur, nxt);
   }
-  const uint64_t nnodes = total << m;
-  range_run(p, st, k_range_tail16<(int)kFdTail, KP>, k_range_tail16_mmo<(int)kFdTail, KP>, grid_for(nnodes, p->cus), cws,
-            cwv, cwt, np1, KP::make(K, (uint32_t)(nroots << m)), nlev - kFdTail, (uint32_t)nnodes, (const uint4*)cur,
-            (uint32_t)skip, (uint32_t)n, (uint4*)ys, ctrs + kRangeCtrs - 1, blocks);
+  const uint64_t nnodes = total << g.m;
+  hipLaunchKernelGGL((k_range_tail16<(int)kFdTail, PRG, KP>), dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock), 0,
+                     st, p->d_tab, rk, cws, cwv, cwt, np1, KP::make(K, (uint32_t)(g.nroots << g.m)), nlev - kFdTail,
+                     (uint32_t)nnodes, (const uint4*)cur, (uint32_t)g.skip, (uint32_t)n, (uint4*)ys,
+                     ctrs + kRangeCtrs - 1, blocks);
   HIP_TRY(hipGetLastError());
   return DCF_OK;
 }
@@ -2226,8 +2248,10 @@ static RangeWideWs range_wide_ws(uint64_t n, uint32_t h, size_t lam) {
   return r;
 }
 
-// One launch group: the n points from xa into ys.  The caller has sized the workspace
-// (range_wide_ws), built the CW digest and zeroed the block count.
+// One launch group: the n points from xa into ys.  MASK: lambda = 32, the kernels' form without
+// t-vectors.  The caller has sized the workspace (range_wide_ws), built the CW digest and zeroed the
+// block count.
+extern "C++" template <bool MASK>
 static int range_wide_group(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
                             const RangeX xa, uint64_t n, uint32_t h, const RangeWideWs& ws, uint8_t* ys) {
   hipStream_t st = L.st;
@@ -2238,61 +2262,42 @@ static int range_wide_group(dcf_prg* p, Lease& L, size_t nb, int party, const ui
   const uint4* dig = (const uint4*)w->d_dig;
   const uint8_t* dig_t = w->d_dig + (size_t)nlev * 64;
   unsigned long long* blocks = reinterpret_cast<unsigned long long*>(w->d_ctr) + 1;
-  uint32_t* tvec = lam > 32 ? reinterpret_cast<uint32_t*>(w->d_ws) : nullptr;
-  const uint64_t cus = (uint64_t)p->cus;
-  const bool mask = lam == 32;
-#define DCF_RW(K, grid, ...)                                                                              \
-  do {                                                                                                    \
-    if (mask) hipLaunchKernelGGL((K<true>), dim3((unsigned)(grid)), dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig, dig_t, __VA_ARGS__); \
-    else hipLaunchKernelGGL((K<false>), dim3((unsigned)(grid)), dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig, dig_t, __VA_ARGS__);     \
-    HIP_TRY(hipGetLastError());                                                                           \
-  } while (0)
+  uint32_t* tvec = MASK ? nullptr : reinterpret_cast<uint32_t*>(w->d_ws);
+  const auto roots_grid = [&](uint64_t roots) { return dim3((unsigned)std::min<uint64_t>((uint64_t)p->cus, (roots + 63) / 64)); };
   if (h == 0) {  // every point is its own root: the root walk writes y[0:32) and the t-vector
-    if (mask) hipLaunchKernelGGL((k_range_roots_wide<true, true>), dim3((unsigned)std::min<uint64_t>(cus, (n + 63) / 64)), dim3(kBlock), 0, st,
-                                 p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, (const uint4*)s0, (uint32_t)party, xa, nlev,
-                                 (uint32_t)n, (uint4*)nullptr, tvec, ys, lam, blocks);
-    else hipLaunchKernelGGL((k_range_roots_wide<true, false>), dim3((unsigned)std::min<uint64_t>(cus, (n + 63) / 64)), dim3(kBlock), 0, st,
-                            p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, (const uint4*)s0, (uint32_t)party, xa, nlev,
-                            (uint32_t)n, (uint4*)nullptr, tvec, ys, lam, blocks);
+    hipLaunchKernelGGL((k_range_roots_wide<true, MASK>), roots_grid(n), dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig, dig_t,
+                       (const uint4*)np1, (const uint4*)s0, (uint32_t)party, xa, nlev, (uint32_t)n, (uint4*)nullptr, tvec,
+                       ys, lam, blocks);
     HIP_TRY(hipGetLastError());
   } else {
-    const uint32_t m = h - kRangeWideTail;  // breadth-first levels below a root
+    const RangeGeom g = range_geom(xa, n, h, kRangeWideTail);
     const uint32_t w0 = (nlev - h + 1) >> 4;  // the t-vector word of the first row below the roots
-    const uint64_t skip = xa.lo & ((1ull << h) - 1);
-    const RangeX pfx{(xa.lo >> h) | (xa.hi << (64 - h)), xa.hi >> h};
-    const uint64_t nroots = ((skip + n - 1) >> h) + 1;  // <= (n >> h) + 2
     uint4* cur = (uint4*)(w->d_ws + ws.tv);
     uint4* nxt = (uint4*)(w->d_ws + ws.tv + ws.buf);
-    uint32_t* tpre = lam > 32 ? (uint32_t*)(w->d_ws + ws.tv + 2 * ws.buf) : nullptr;
+    uint32_t* tpre = MASK ? nullptr : (uint32_t*)(w->d_ws + ws.tv + 2 * ws.buf);
     uint32_t* ctrs = (uint32_t*)(w->d_ws + ws.tv + 2 * ws.buf + ws.pre);
     HIP_TRY(hipMemsetAsync(ctrs, 0, kRangeCtrs * sizeof(uint32_t), st));
-    if (mask) hipLaunchKernelGGL((k_range_roots_wide<false, true>), dim3((unsigned)std::min<uint64_t>(cus, (nroots + 63) / 64)), dim3(kBlock), 0,
-                                 st, p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, (const uint4*)s0, (uint32_t)party, pfx,
-                                 nlev - h, (uint32_t)nroots, cur, tpre, (uint8_t*)nullptr, lam, blocks);
-    else hipLaunchKernelGGL((k_range_roots_wide<false, false>), dim3((unsigned)std::min<uint64_t>(cus, (nroots + 63) / 64)), dim3(kBlock), 0,
-                            st, p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, (const uint4*)s0, (uint32_t)party, pfx,
-                            nlev - h, (uint32_t)nroots, cur, tpre, (uint8_t*)nullptr, lam, blocks);
+    hipLaunchKernelGGL((k_range_roots_wide<false, MASK>), roots_grid(g.nroots), dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig,
+                       dig_t, (const uint4*)np1, (const uint4*)s0, (uint32_t)party, g.pfx, nlev - h, (uint32_t)g.nroots, cur,
+                       tpre, (uint8_t*)nullptr, lam, blocks);
     HIP_TRY(hipGetLastError());
-    for (uint32_t k = 0; k < m; ++k) {  // level 8N - h + k: nroots << k parents
-      const uint64_t parents = nroots << k;
-      DCF_RW(k_range_level_wide, grid_for(parents, p->cus), nlev - h + k, w0, (uint32_t)parents, (const uint4*)cur, nxt,
-             ctrs + k, blocks);
+    for (uint32_t k = 0; k < g.m; ++k) {  // level 8N - h + k: nroots << k parents
+      const uint64_t parents = g.nroots << k;
+      hipLaunchKernelGGL((k_range_level_wide<MASK>), dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st,
+                         p->d_tab, p->d_rk2, dig, dig_t, nlev - h + k, w0, (uint32_t)parents, (const uint4*)cur, nxt, ctrs + k,
+                         blocks);
+      HIP_TRY(hipGetLastError());
       std::swap(cur, nxt);
     }
-    const uint64_t nnodes = nroots << m;
+    const uint64_t nnodes = g.nroots << g.m;
     const uint32_t nq = ((nlev >> 4) + 1 + 3) / 4;  // uint4s holding rows 0 .. 8N of a t-vector
-    if (mask) hipLaunchKernelGGL((k_range_tail_wide<(int)kRangeWideTail, true>), dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock), 0, st,
-                                 p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, nlev - kRangeWideTail, w0, (uint32_t)nnodes,
-                                 (const uint4*)cur, (uint32_t)skip, (uint32_t)n, ys, lam, (uint4*)tvec, (const uint4*)tpre, m, nq,
-                                 ctrs + kRangeCtrs - 1, blocks);
-    else hipLaunchKernelGGL((k_range_tail_wide<(int)kRangeWideTail, false>), dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock), 0, st,
-                            p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, nlev - kRangeWideTail, w0, (uint32_t)nnodes,
-                            (const uint4*)cur, (uint32_t)skip, (uint32_t)n, ys, lam, (uint4*)tvec, (const uint4*)tpre, m, nq,
-                            ctrs + kRangeCtrs - 1, blocks);
+    hipLaunchKernelGGL((k_range_tail_wide<(int)kRangeWideTail, MASK>), dim3((unsigned)grid_for(nnodes, p->cus)),
+                       dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, nlev - kRangeWideTail, w0,
+                       (uint32_t)nnodes, (const uint4*)cur, (uint32_t)g.skip, (uint32_t)n, ys, lam, (uint4*)tvec,
+                       (const uint4*)tpre, g.m, nq, ctrs + kRangeCtrs - 1, blocks);
     HIP_TRY(hipGetLastError());
   }
-#undef DCF_RW
-  if (lam > 32)  // y[32, lambda) from the t-vectors (the existing tail kernels)
+  if (!MASK)  // y[32, lambda) from the t-vectors (the existing tail kernels)
     return run_tail(cwb, cwv, np1, s0, nlev, lam, 1, 0, tvec, n, ys, st, p->cus, n, party, w);
   return DCF_OK;
 }
@@ -2304,32 +2309,26 @@ static int range_wide_launch(dcf_prg* p, Lease& L, size_t nb, int party, const u
   hipStream_t st = L.st;
   Workspace* w = L.w;
   const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * nb);
-  if (int rc = ensure_ctr(w)) return rc;
-  const uint64_t group = range_wide_points(nb);
-  const RangeWideWs ws = range_wide_ws(std::min<uint64_t>(cnt, group), h, lam);
-  if (int rc = ensure_ws(w, ws.total, st)) return rc;
+  const uint64_t per = range_wide_points(nb);
+  const RangeWideWs ws = range_wide_ws(std::min<uint64_t>(cnt, per), h, lam);
   if (w->dig_levels < nlev) {
     size_t have = (size_t)w->dig_levels * 65;
     if (int rc = grow(&w->d_dig, &have, (size_t)nlev * 65, st)) return rc;
     w->dig_levels = nlev;
   }
-  if (zero_blocks) HIP_TRY(hipMemsetAsync(w->d_ctr, 0, kCtrBytes, st));
-  w->last_prefix = 0;
-  phase_mark(p, L, 0);
+  if (int rc = range_begin(p, L, ws.total, zero_blocks)) return rc;
   // CW digest of the key, once per call: bytes [0,32) of each level's cw_s / cw_v, and cw_t
   hipLaunchKernelGGL(k_cw_digest, dim3((4 * nlev + 255) / 256), dim3(256), 0, st, cwb, cwb + (size_t)nlev * lam,
                      cwb + 2 * (size_t)nlev * lam, nlev, lam, (uint64_t)1, (uint64_t)0, 1u, (uint4*)w->d_dig,
                      w->d_dig + (size_t)nlev * 64);
   HIP_TRY(hipGetLastError());
   phase_mark(p, L, 1);
-  for (uint64_t o = 0; o < cnt; o += group) {  // h = 0: cnt < 2^12, one group
-    const uint64_t n = std::min<uint64_t>(group, cnt - o);
-    if (int rc = range_wide_group(p, L, nb, party, cwb, s0, range_add(A.x, off + o), n, h, ws, ys + o * (uint64_t)lam))
-      return rc;
+  const auto group = lam == 32 ? range_wide_group<true> : range_wide_group<false>;
+  for (uint64_t o = 0; o < cnt; o += per) {  // h = 0: cnt < 2^12, one group
+    const uint64_t n = std::min<uint64_t>(per, cnt - o);
+    if (int rc = group(p, L, nb, party, cwb, s0, range_add(A.x, off + o), n, h, ws, ys + o * (uint64_t)lam)) return rc;
   }
-  phase_mark(p, L, 2);
-  p->last_ws.store(w);
-  return DCF_OK;
+  return range_end(p, L);
 }
 
 // Points [off, off + cnt) of the range into ys (the output of point `off`), on L.st.  h: the
@@ -2352,24 +2351,16 @@ static int range_launch(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_
     HIP_TRY(hipStreamSynchronize(st));  // xs is freed on return
     return DCF_OK;
   }
-  Workspace* w = L.w;
-  if (int rc = ensure_ctr(w)) return rc;
   size_t buf_bytes;
-  if (const size_t ws = range_ws_bytes(1, std::min<uint64_t>(cnt, kRangeLaunch), h, &buf_bytes))
-    if (int rc = ensure_ws(w, ws, st)) return rc;
-  if (zero_blocks) HIP_TRY(hipMemsetAsync(w->d_ctr, 0, kCtrBytes, st));
-  w->last_prefix = 0;
-  phase_mark(p, L, 0);
+  const size_t ws = range_ws_bytes(1, std::min<uint64_t>(cnt, kRangeLaunch), h, &buf_bytes);
+  if (int rc = range_begin(p, L, ws, zero_blocks)) return rc;
   phase_mark(p, L, 1);
+  const auto group = p->kind == 0 ? range_group<RangeHirose, RangeOneKey> : range_group<RangeMmo, RangeOneKey>;
   for (uint64_t o = 0; o < cnt; o += kRangeLaunch) {  // h = 0: cnt < 2^12, one pass
     const uint64_t n = std::min<uint64_t>(kRangeLaunch, cnt - o);
-    if (int rc = range_group<RangeOneKey>(p, L, nb, 1, party, cwb, s0, 0, 1, range_add(A.x, off + o), n, h, buf_bytes,
-                                          ys + o * lam))
-      return rc;
+    if (int rc = group(p, L, nb, 1, party, cwb, s0, 0, 1, range_add(A.x, off + o), n, h, buf_bytes, ys + o * lam)) return rc;
   }
-  phase_mark(p, L, 2);
-  p->last_ws.store(w);
-  return DCF_OK;
+  return range_end(p, L);
 }
 
 int dcf_eval_range_device(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
@@ -2494,36 +2485,29 @@ int dcf_eval_range_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, 
   if (int rc = L.order((hipStream_t)stream)) return rc;
   if (p->lambda != 16 || n_bytes > 16)
     return rangemk_fallback(p, L, n_bytes, num_keys, party, cwb, s0s, A, count, ys);
-  Workspace* w = L.w;
-  if (int rc = ensure_ctr(w)) return rc;
   const uint32_t h = rangemk_levels(n_bytes, num_keys, count);
   const uint64_t per = std::min<uint64_t>(num_keys, rangemk_keys_per_launch(h, count));
   size_t buf_bytes;
-  if (const size_t ws = range_ws_bytes(per, std::min<uint64_t>(count, kRangeLaunch), h, &buf_bytes))
-    if (int rc = ensure_ws(w, ws, L.st)) return rc;
-  HIP_TRY(hipMemsetAsync(w->d_ctr, 0, kCtrBytes, L.st));
-  w->last_prefix = 0;
-  phase_mark(p, L, 0);
+  const size_t ws = range_ws_bytes(per, std::min<uint64_t>(count, kRangeLaunch), h, &buf_bytes);
+  if (int rc = range_begin(p, L, ws, true)) return rc;
   phase_mark(p, L, 1);
+  const auto group = p->kind == 0 ? range_group<RangeHirose, RangeKeys> : range_group<RangeMmo, RangeKeys>;
   if ((count >> h) + 2 <= (kRangeLaunch >> h)) {  // groups of whole keys
     for (uint64_t k0 = 0; k0 < num_keys; k0 += per) {
       const uint64_t keys = std::min<uint64_t>(per, num_keys - k0);
-      if (int rc = range_group<RangeKeys>(p, L, n_bytes, num_keys, party, cwb, s0s, k0, keys, A.x, count, h, buf_bytes,
-                                 ys + k0 * count * 16))
+      if (int rc = group(p, L, n_bytes, num_keys, party, cwb, s0s, k0, keys, A.x, count, h, buf_bytes, ys + k0 * count * 16))
         return rc;
     }
   } else {  // one key alone exceeds a launch: the keys one after another, 2^28 outputs at a time
     for (uint64_t k = 0; k < num_keys; ++k)
       for (uint64_t o = 0; o < count; o += kRangeLaunch) {
         const uint64_t n = std::min<uint64_t>(kRangeLaunch, count - o);
-        if (int rc = range_group<RangeKeys>(p, L, n_bytes, num_keys, party, cwb, s0s, k, 1, range_add(A.x, o), n, h, buf_bytes,
-                                   ys + (k * count + o) * 16))
+        if (int rc = group(p, L, n_bytes, num_keys, party, cwb, s0s, k, 1, range_add(A.x, o), n, h, buf_bytes,
+                           ys + (k * count + o) * 16))
           return rc;
       }
   }
-  phase_mark(p, L, 2);
-  p->last_ws.store(w);
-  return DCF_OK;
+  return range_end(p, L);
 }
 
 int dcf_gen(dcf_prg* p, size_t n_bytes, const uint8_t* alpha, const uint8_t* beta, const uint8_t* s0_0,

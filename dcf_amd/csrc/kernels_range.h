@@ -20,8 +20,10 @@
 //                     leaf's output index is its distance from x0 and leaves outside the range are
 //                     not stored.
 // Each is a template on the key policy, RangeOneKey or RangeKeys, and is instantiated for both.
-// kernels_range_mmo.h has the three stages over the MMO PRG, on the same key policies;
-// kernels_range_wide.h has them over the Hirose PRG's head state at LAMBDA >= 32, for one key.
+// k_range_level16 and k_range_tail16 are also templates on the PRG policy: RangeHirose here,
+// RangeMmo in kernels_range_mmo.h, which has the MMO PRG's own root walk (k_range_roots16_mmo)
+// as well.  kernels_range_wide.h has the three stages over the Hirose PRG's head state at
+// LAMBDA >= 32, for one key.
 //   k_range_points    the points x0 + i as N-byte big-endian strings, for the MMO PRG at
 //                     LAMBDA >= 32 and for N > 16, which have no tree-sharing path (the existing
 //                     eval runs on them).
@@ -159,18 +161,41 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_roots16(
   }
 }
 
+// PRG policies of the level and tail kernels: what differs between the Hirose PRG (here) and the
+// MMO PRG (RangeMmo, kernels_range_mmo.h).
+//   Arg        the kernels' key argument, and arg(p) its value for a dcf_prg (the host's type)
+//   keys()     the kernel's set-up of the keys, ahead of lds_fill_tables; what children() takes
+//   children   both children of a node under the correction words of its level
+//   kBlocks    AES blocks per node
+//   kPacked    the tail keeps t in the node's word 3 under every key policy, not only per-lane keys
+//   roots()    the PRG's root kernel; kRootsPer roots fill a workgroup before a second one pays
+struct RangeHirose {
+  using Arg = RoundKeys;  // by value: SGPRs
+  static constexpr unsigned long long kBlocks = 2;
+  static constexpr bool kPacked = false;
+  static constexpr uint64_t kRootsPer = kBlock / 32;  // a pass of half-waves (RowPrg)
+  template <class Prg>
+  static Arg arg(const Prg* p) { return p->rk[0]; }
+  template <bool LEAF, class KP>
+  static auto roots() { return k_range_roots16<LEAF, KP>; }
+  static __device__ __forceinline__ const RoundKeys& keys(const RoundKeys& rk) { return rk; }
+  template <class... A>
+  static __device__ __forceinline__ void children(A&&... a) { fd_children(a...); }
+};
+
 // Interior, one launch per level (k_fd_level16 on PrefixTable-style rows): the parents of level
 // `lev` — rows in[2j], in[2j + 1] of all blocks of all keys, consecutive in leaf order — become the
 // children rows out[4j .. 4j + 3], one lane per parent, waves claiming units of parents from
-// ctr[0].  blocks: the call's AES block count, 2 per parent.
-template <class KP>
+// ctr[0].  blocks: the call's AES block count, PRG::kBlocks per parent.
+template <class PRG, class KP>
 __global__ __launch_bounds__(kBlock, 1) void k_range_level16(
-    const uint32_t* __restrict__ tab, const RoundKeys rk, const uint4* __restrict__ cw_s,
+    const uint32_t* __restrict__ tab, const typename PRG::Arg rk, const uint4* __restrict__ cw_s,
     const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const KP kp, const uint32_t lev,
     const uint32_t nparents, const uint4* __restrict__ in, uint4* __restrict__ out, uint32_t* __restrict__ ctr,
     unsigned long long* __restrict__ blocks) {
   __shared__ uint32_t lds[kLdsWords];
-  lds_fill_tables(lds, tab);
+  const auto& ks = PRG::keys(rk);
+  lds_fill_tables(lds, tab);  // its barrier also publishes the keys
   const uint32_t lc = lane_const();
   uint32_t csw[4], cvw[4], ct = 0u;
   if constexpr (!KP::kPerLane) ct = fd_cw(cw_s, cw_v, cw_t, kp.cw(lev, 0u), csw, cvw);
@@ -186,7 +211,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_level16(
     const uint4 a = in[2ull * jj], b = in[2ull * jj + 1u];
     const uint32_t s[4] = {a.x, a.y, a.z, a.w & kMaskLast}, v[4] = {b.x, b.y, b.z, b.w};
     uint32_t sl[4], vl[4], sr[4], vr[4], tl, tr;
-    fd_children(lds, lc, rk, csw, cvw, ct, s, v, (a.w >> 24) & 1u, sl, vl, tl, sr, vr, tr);
+    PRG::children(lds, lc, ks, csw, cvw, ct, s, v, (a.w >> 24) & 1u, sl, vl, tl, sr, vr, tr);
     if (!live) continue;
     uint4* o = out + 4ull * j;
     o[0] = make_uint4(sl[0], sl[1], sl[2], (sl[3] & kMaskLast) | (tl << 24));
@@ -194,7 +219,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_level16(
     o[2] = make_uint4(sr[0], sr[1], sr[2], (sr[3] & kMaskLast) | (tr << 24));
     o[3] = make_uint4(vr[0], vr[1], vr[2], vr[3]);
   }
-  if ((threadIdx.x & 63u) == 0 && nlive) atomicAdd(blocks, 2ull * nlive);
+  if ((threadIdx.x & 63u) == 0 && nlive) atomicAdd(blocks, PRG::kBlocks * nlive);
 }
 
 // Tail: k_fd_dfs16's register depth-first expansion of the last H levels from the rows of level
@@ -205,20 +230,21 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_level16(
 // `skip` leaves in and holds `count`, so leaf g is the key's output g - skip, stored at
 // ys[key * count + g - skip] only when g - skip is below count (32-bit: a launch covers at most
 // 2^28 outputs; g < skip wraps far above).
-// PACKED (per-lane correction words): the node and the stack slots stay in the rows' form, 8 words
-// with t in bit 24 of word 3, the bit s has cleared; the words take the registers that a separate t
-// (9-word nodes) has otherwise.
-// blocks: the call's AES block count, 2 (2^H - 1) per node — clipped leaves included.
-template <int H, class KP>
+// PACKED (per-lane correction words, and the MMO PRG always): the node and the stack slots stay in
+// the rows' form, 8 words with t in bit 24 of word 3, the bit s has cleared; the words take the
+// registers that a separate t (9-word nodes) has otherwise.
+// blocks: the call's AES block count, PRG::kBlocks (2^H - 1) per node — clipped leaves included.
+template <int H, class PRG, class KP>
 __global__ __launch_bounds__(kBlock, 1) void k_range_tail16(
-    const uint32_t* __restrict__ tab, const RoundKeys rk, const uint4* __restrict__ cw_s,
+    const uint32_t* __restrict__ tab, const typename PRG::Arg rk, const uint4* __restrict__ cw_s,
     const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const uint4* __restrict__ cw_np1,
     const KP kp, const uint32_t lev0, const uint32_t nnodes, const uint4* __restrict__ rows, const uint32_t skip,
     const uint32_t count, uint4* __restrict__ ys, uint32_t* __restrict__ ctr,
     unsigned long long* __restrict__ blocks) {
   static_assert(H >= 2 && H <= 4, "register depth-first tail of 2..4 levels");
-  constexpr bool PACKED = KP::kPerLane;
+  constexpr bool PACKED = PRG::kPacked || KP::kPerLane;
   __shared__ uint32_t lds[kLdsWords];
+  const auto& ks = PRG::keys(rk);
   lds_fill_tables(lds, tab);
   const uint32_t lc = lane_const();
   const uint4 np0 = KP::kPerLane ? make_uint4(0u, 0u, 0u, 0u) : cw_np1[0];
@@ -262,7 +288,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_tail16(
         if constexpr (PACKED) t = (n[3] >> 24) & 1u;
         else t = n[8];
         uint32_t sl[4], vl[4], sr[4], vr[4], tl, tr;
-        fd_children(lds, lc, rk, csw, cvw, cw_t[c], s, v, t, sl, vl, tl, sr, vr, tr);
+        PRG::children(lds, lc, ks, csw, cvw, cw_t[c], s, v, t, sl, vl, tl, sr, vr, tr);
         if (k + 1u == (uint32_t)H) {  // leaves 2i, 2i + 1 of the node: y = v ^ s ^ t * cw_np1 (lib.rs:192)
           const uint32_t ol = o0 + 2u * i, orr = ol + 1u;
           const uint32_t ml = 0u - tl, mr = 0u - tr;
@@ -295,7 +321,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_tail16(
       }
     }
   }
-  if ((threadIdx.x & 63u) == 0 && nlive) atomicAdd(blocks, 2ull * ((1u << H) - 1u) * nlive);
+  if ((threadIdx.x & 63u) == 0 && nlive) atomicAdd(blocks, PRG::kBlocks * ((1u << H) - 1u) * nlive);
 }
 
 // Points x0 + i, i in [0, count), as N-byte big-endian strings (a sibling of k_domain_points): the

@@ -32,6 +32,8 @@
 // Every t-vector row is written as whole uint4s, zero past row 8N.  All node, root and output
 // indices of a launch are 32-bit (the host keeps a launch group <= 2^28 outputs).  blocks: the
 // call's AES-256 block count, 4 per stepped node, one atomic per wave.
+// MASK (LAMBDA = 32: no t-vectors) is chosen once per call on the host (range_wide_group<MASK>),
+// which takes a group's blocks from the same range_geom as the LAMBDA = 16 path.
 #pragma once
 
 #include "aes_lds.h"

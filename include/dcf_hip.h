@@ -311,8 +311,8 @@ int dcf_eval_full_domain_device(dcf_prg* prg, size_t n_bytes, int party, const u
  *   a launch in all.
  *   dcf_prg_last_eval_blocks then reports the AES blocks of the root paths, the interior
  *   expansion and the tail, clipped leaves of the edge blocks included.
- *   MMO PRG, lambda = 16, N <= 16: the same blocks, heights, launches and workspace with the MMO
- *   kernels (kernels_range_mmo.h); a node's two children cost four AES-128 blocks and a step of a
+ *   MMO PRG, lambda = 16, N <= 16: the same blocks, heights, launches, workspace and level and
+ *   tail kernels under the MMO policy, with its own root walk (kernels_range_mmo.h); a node's two children cost four AES-128 blocks and a step of a
  *   root walk two, so 4 AES-128 blocks per output plus 2 (8N - h) per root instead of 32N per
  *   point, and h = 0 walks every point in one launch.  Asynchronous on `stream` like the Hirose
  *   path: no materialised points, no stream wait.  dcf_prg_last_eval_blocks then reports the

@@ -1,6 +1,7 @@
 """The MMO range-eval tree path restated in Python on OracleMmoPrg.gen, without a GPU: the root walk
 (two blocks per level), the breadth-first level expansion on packed 32-byte rows with t in bit 24
-of the seed's last word, and the clipped leaves of the depth-first tail (kernels_range_mmo.h).
+of the seed's last word, and the clipped leaves of the depth-first tail (kernels_range_mmo.h and
+the RangeMmo instances of kernels_range.h).
 
 It pins the row format: every child seed has bit 0 of byte 15 cleared by the PRG and cw_s is the XOR
 of two such seeds, so that bit is free in every row the stages write; v is not clean, so t cannot

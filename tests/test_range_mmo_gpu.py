@@ -1,5 +1,5 @@
-"""Range eval over the Matyas-Meyer-Oseas AES-128 PRG on the GPU (kernels_range_mmo.h), one key and
-K keys: dcf_eval_range_device / dcf_eval_range / dcf_eval_range_multikey_device against the CPU
+"""Range eval over the Matyas-Meyer-Oseas AES-128 PRG on the GPU (kernels_range_mmo.h and the
+RangeMmo instances of kernels_range.h), one key and K keys: dcf_eval_range_device / dcf_eval_range / dcf_eval_range_multikey_device against the CPU
 oracle on the points (x0 + i).to_bytes(N, "big"), bit for bit, on keys from the oracle's gen over
 OracleMmoPrg.  Every case evaluates both parties, checks the 64 sentinel rows on either side of ys,
 that the parties' outputs reconstruct the comparison function on all rows, and the AES-128 block

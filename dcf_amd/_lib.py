@@ -36,7 +36,7 @@ EXPORTS = [
     "dcf_prg_device_bytes", "dcf_prg_host_pinned_bytes", "dcf_prg_workspaces", "dcf_prg_trim", "dcf_prg_set_phase_timing",
     "dcf_prg_last_eval_phases", "dcf_eval_range_device", "dcf_eval_range", "dcf_eval_range_subtree_levels",
     "dcf_eval_range_multikey_device", "dcf_eval_range_multikey_subtree_levels", "dcf_eval_range_keys_per_launch",
-    "dcf_eval_range_wide_points_per_launch",
+    "dcf_eval_range_wide_points_per_launch", "dcf_prefix_deepen_calls", "dcf_prefix_reuse_max_depth",
 ]
 
 
@@ -100,6 +100,8 @@ def load(path: str = LIB_PATH):
         "dcf_share_from_bincode": ([sz, sz, u8p, sz, u8p, u8p, sz, ctypes.POINTER(sz)], i),
         "dcf_point_slice": ([sz, sz, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)], None),
         "dcf_prg_set_prefix_max_bytes": ([vp, sz], i),
+        "dcf_prefix_deepen_calls": ([i, sz], ctypes.c_uint64),
+        "dcf_prefix_reuse_max_depth": ([sz, sz, sz], i),
         "dcf_prg_device_bytes": ([vp], sz),
         "dcf_prg_host_pinned_bytes": ([vp], sz),
         "dcf_prg_workspaces": ([vp], i),

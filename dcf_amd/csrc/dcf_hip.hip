@@ -146,6 +146,25 @@ struct Workspace {
   hipEvent_t tev[3] = {};
   bool timed = false;
   uint32_t last_prefix = 0;
+  // Cross-call shared-prefix table (dcf_eval_device, one key, LAMBDA = 16 Hirose; reuse_prefix):
+  // the device state (valid depth + the key material the table in d_pfx was built from,
+  // kernels16.h) and the host's hints.  The verdict "same key" lives on the device only; the host
+  // knows what it asked for, not what the device found.
+  uint32_t* d_pst = nullptr;
+  bool last_prefix_dev = false;  // last_prefix is the host's guess: d_pst[0] holds the depth walked
+  struct PrefixHints {
+    bool valid = false;          // d_pfx holds this path's table (any other user of d_pfx clears it)
+    const void* cwb = nullptr;
+    const void* s0 = nullptr;
+    int party = 0;
+    size_t n_bytes = 0;
+    uint32_t req = 0;            // first-call depth asked for (prefix_depth of the call)
+    uint32_t base = 0;           // first-call depth built (a rebuild goes back to it)
+    uint32_t depth = 0;          // depth the table should have now
+    uint64_t calls = 0;          // calls walked at `depth`
+    bool grow = true;            // false once an allocation for a deeper table failed
+    uint64_t epoch = 0;          // the prg's settings epoch the hints belong to
+  } ph;
 };
 
 struct dcf_prg {
@@ -166,6 +185,8 @@ struct dcf_prg {
   std::atomic<int> prefix_levels{-1};     // shared-prefix table depth: -1 auto, 0 off
   std::atomic<size_t> prefix_cap{0};      // dcf_prg_set_prefix_max_bytes (0 = none)
   std::atomic<int> timing{0};             // dcf_prg_set_phase_timing
+  std::atomic<uint64_t> epoch{1};         // bumped by the setters that reset the cross-call table state
+  size_t total_mem = 0;                   // the device's memory (cap on the cross-call table: 1/8 of it)
   // Workspace pool (see Workspace).
   std::mutex pool_mu;
   std::vector<Workspace*> all_ws, free_ws;
@@ -180,9 +201,12 @@ struct Cfg {
   int mode, prefix_levels;
   size_t prefix_cap;
   bool timing;
+  uint64_t epoch;
 };
 Cfg snapshot(const dcf_prg* p) {
-  return Cfg{p->eval_mode.load(), p->prefix_levels.load(), p->prefix_cap.load(), p->timing.load() != 0};
+  // (the epoch first: a setter bumps it after storing, so a call never pairs a new epoch with an old setting)
+  const uint64_t epoch = p->epoch.load();
+  return Cfg{p->eval_mode.load(), p->prefix_levels.load(), p->prefix_cap.load(), p->timing.load() != 0, epoch};
 }
 
 // A workspace leased for one call.  `st` is the stream the call's device work is queued on
@@ -194,6 +218,7 @@ struct Lease {
   hipStream_t st = nullptr;
   bool ordered = false;
   bool drained = false;  // a host call synchronized its streams: nothing left to order after
+  bool reuse = false;    // dcf_eval_device: the shared-prefix table may outlive the call (reuse_prefix)
   Lease(dcf_prg* prg) : p(prg), c(snapshot(prg)) {
     {
       std::lock_guard<std::mutex> g(p->pool_mu);
@@ -327,13 +352,16 @@ uint32_t prefix_region_log2(uint32_t d, uint32_t S) {
 
 // Device bytes of a shared-prefix table of depth d (table + build buffers, as build_prefix /
 // build_wide_prefix allocate them).
-size_t prefix_table_bytes(const dcf_prg* p, uint32_t d) {
-  if (d == 0) return 0;
+size_t hirose16_table_bytes(uint32_t d) {  // Hirose, LAMBDA = 16: k_prefix_build16's table + buffers
   const uint32_t S = prefix_split(d);
-  if (p->lambda > 16) return (((size_t)80 << d) + 255) + 2 * ((size_t)80 << (d - 1u));
-  if (p->kind == 1) return 2 * ((((size_t)33 << d) + 255) & ~(size_t)255) + 256;
   return ((((size_t)32 << d) + 255) & ~(size_t)255) +
          2 * ((size_t)1 << S) * ((((size_t)33 << prefix_region_log2(d, S)) + 255) & ~(size_t)255);
+}
+size_t prefix_table_bytes(const dcf_prg* p, uint32_t d) {
+  if (d == 0) return 0;
+  if (p->lambda > 16) return (((size_t)80 << d) + 255) + 2 * ((size_t)80 << (d - 1u));
+  if (p->kind == 1) return 2 * ((((size_t)33 << d) + 255) & ~(size_t)255) + 256;
+  return hirose16_table_bytes(d);
 }
 
 // Auto depth under the dcf_prg_set_prefix_max_bytes cap: shallower until it fits (none below 8).
@@ -423,6 +451,7 @@ int build_wide_prefix(dcf_prg* p, Workspace* w, uint32_t nlev, int party, const 
   const size_t tab_bytes = (((size_t)80 << levels) + 255) & ~(size_t)255;
   const size_t region = (size_t)80 * R;
   const size_t need = tab_bytes + 2 * ((size_t)1 << S) * region;
+  w->ph.valid = false;  // d_pfx changes hands
   if (int rc = grow(&w->d_pfx, &w->pfx_bytes, need, st)) return rc;
   uint4* table = (uint4*)w->d_pfx;
   uint4* ba = (uint4*)(w->d_pfx + tab_bytes);
@@ -444,9 +473,12 @@ int build_wide_prefix(dcf_prg* p, Workspace* w, uint32_t nlev, int party, const 
 // Expand the top `levels` levels of the key's tree (s = s0, v = 0, t = party at the
 // root; k_fd_level16 per level, as the full-domain eval does) into w->d_pfx.
 
+// pst (reuse_prefix, Hirose only): the gated build, which runs only if the device state word says
+// that no table is valid; reuse_prefix sets the hints again afterwards.
 int build_prefix(dcf_prg* p, Workspace* w, size_t n_bytes, int party, const uint4* cws, const uint4* cwv,
                  const uint8_t* cwt, const uint4* np1, const uint8_t* s0, uint32_t levels, PrefixTable* out,
-                 hipStream_t st) {
+                 hipStream_t st, const uint32_t* pst = nullptr) {
+  w->ph.valid = false;  // d_pfx changes hands
   const uint64_t maxnodes = 1ull << levels;
   const size_t nodeb = 33, half = (maxnodes * nodeb + 255) & ~(size_t)255;
   // Hirose: [table 2^D x 32 B | 2 x 2^S regions of 2^(D-1-S) nodes]; MMO: two level buffers + counters
@@ -473,9 +505,14 @@ int build_prefix(dcf_prg* p, Workspace* w, size_t n_bytes, int party, const uint
   if (p->kind == 0) {  // one launch: k_prefix_build16
     uint8_t* ba = w->d_pfx + tab_bytes;
     const uint32_t H = prefix_dfs_levels(levels, S);
-    hipLaunchKernelGGL(k_prefix_build16, dim3(1u << S), dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt,
-                       (const uint4*)s0, (uint32_t)party, S, levels, H, ba, ba + ((size_t)1 << S) * region,
-                       (uint64_t)region, R, (uint4*)w->d_pfx, p->d_rk0);
+    if (pst)
+      hipLaunchKernelGGL(k_prefix_build16<true>, dim3(1u << S), dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt,
+                         (const uint4*)s0, (uint32_t)party, S, levels, H, ba, ba + ((size_t)1 << S) * region,
+                         (uint64_t)region, R, (uint4*)w->d_pfx, p->d_rk0, pst);
+    else
+      hipLaunchKernelGGL(k_prefix_build16<false>, dim3(1u << S), dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt,
+                         (const uint4*)s0, (uint32_t)party, S, levels, H, ba, ba + ((size_t)1 << S) * region,
+                         (uint64_t)region, R, (uint4*)w->d_pfx, p->d_rk0, (const uint32_t*)nullptr);
     HIP_TRY(hipGetLastError());
     *out = PrefixTable{(const uint4*)w->d_pfx, levels};
     return DCF_OK;
@@ -517,15 +554,168 @@ int build_prefix(dcf_prg* p, Workspace* w, size_t n_bytes, int party, const uint
 // build_prefix at depth d; in auto mode (prefix_levels < 0) an allocation failure retries
 // two levels shallower, down to 8, and then evaluates without a table (same output bytes).
 int try_prefix(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, int party, const uint4* cws, const uint4* cwv,
-               const uint8_t* cwt, const uint4* np1, const uint8_t* s0, uint32_t d, PrefixTable* out, hipStream_t st) {
+               const uint8_t* cwt, const uint4* np1, const uint8_t* s0, uint32_t d, PrefixTable* out, hipStream_t st,
+               const uint32_t* pst = nullptr) {
   *out = PrefixTable{nullptr, 0u};
   while (d) {
-    const int rc = build_prefix(p, w, n_bytes, party, cws, cwv, cwt, np1, s0, d, out, st);
+    const int rc = build_prefix(p, w, n_bytes, party, cws, cwv, cwt, np1, s0, d, out, st, pst);
     if (rc != kPrefixNoMem) return rc;
     if (c.prefix_levels >= 0) return fail(DCF_ERR_HIP, t_err);  // a forced depth must fit
     d = d >= 10u ? d - 2u : 0u;
   }
   *out = PrefixTable{nullptr, 0u};
+  return DCF_OK;
+}
+
+// ---- Cross-call shared-prefix table (dcf_eval_device: one key, LAMBDA = 16, Hirose, N = 16 / 4) ----
+// All of a call's table work depends on the key alone, and the real use (one key, points arriving
+// batch after batch) keeps the key: the table is kept across calls, not rebuilt while the key
+// material is unchanged (decided on the device, k_prefix_check), and once its build is sunk it is
+// deepened one level at a time, each level sparing every later point one level of the walk.
+//
+// Deepening D -> D + 1 costs 2^(D+1) blocks once and spares a call of m points 1.257 m blocks (the
+// walk's blocks per level): it has paid for itself after
+// ceil(2^(D+1) / (1.257 m)) calls, and the host deepens at the start of a call once that many calls
+// have walked at D.
+constexpr uint64_t kWalkMilliBlocksPerLevel = 1257;
+
+}  // namespace
+
+uint64_t dcf_prefix_deepen_calls(int depth, size_t points) {
+  if (depth < 0 || depth >= (int)kPfxKeyLevels || points == 0) return 0;
+  const uint64_t num = (1000ull << (depth + 1)), den = kWalkMilliBlocksPerLevel * (uint64_t)points;
+  return std::max<uint64_t>(1, (num + den - 1) / den);
+}
+
+int dcf_prefix_reuse_max_depth(size_t n_bytes, size_t device_bytes, size_t cap_bytes) {
+  if (n_bytes == 0) return 0;
+  uint32_t d = (uint32_t)std::min<size_t>(kPfxKeyLevels, 8 * n_bytes - 1);
+  // the dcf_prg_set_prefix_max_bytes cap keeps its meaning: what a table of that depth takes when
+  // one call builds it (table + build buffers), although a deepened table has no build buffers
+  while (d && ((((size_t)32 << d) > device_bytes / 8) || (cap_bytes && hirose16_table_bytes(d) > cap_bytes))) --d;
+  return (int)d;
+}
+
+namespace {
+
+void launch_commit(Workspace* w, hipStream_t st, uint32_t expect, uint32_t depth, uint32_t other, uint64_t blocks) {
+  hipLaunchKernelGGL(k_prefix_commit, dim3(1), dim3(1), 0, st, w->d_pst, w->d_ctr, expect, depth, other, blocks);
+}
+
+// The table of a dcf_eval_device call of `total` points whose one-call depth is d (prefix_depth).
+// *out: the table and the depth the host expects; the walk reads the real depth from w->d_pst.
+// out->levels = 0: no table could be allocated, the walk starts at the root.
+int reuse_prefix(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, int party, const uint8_t* cwb,
+                 const uint4* cws, const uint4* cwv, const uint8_t* cwt, const uint4* np1, const uint8_t* s0,
+                 uint32_t d, uint64_t total, PrefixTable* out, hipStream_t st) {
+  Workspace::PrefixHints& h = w->ph;
+  // dcf_prg_last_eval_blocks: at automatic depth the table is the library's own choice and part of
+  // what the call encrypts, so the build / deepening that really ran is counted; a forced depth
+  // reports the walk alone, as every other path does
+  const uint64_t counted = c.prefix_levels < 0 ? 1u : 0u;
+  if (!w->d_pst) {
+    HIP_TRY(hipMalloc(&w->d_pst, kPfxStateBytes));  // (written whole by the first, forced, check)
+    h.valid = false;
+  }
+  const uint32_t nlev = std::min<uint32_t>(kPfxKeyLevels, (uint32_t)(8 * n_bytes - 1));
+  const bool same = h.valid && h.cwb == cwb && h.s0 == s0 && h.party == party && h.n_bytes == n_bytes &&
+                    h.req == d && h.epoch == c.epoch && w->d_pfx &&
+                    w->pfx_bytes >= std::max(prefix_table_bytes(p, h.base), (size_t)32 << h.depth);
+  auto check = [&](uint32_t force) {
+    hipLaunchKernelGGL(k_prefix_check, dim3(1), dim3(256), 0, st, (const uint8_t*)cws, (const uint8_t*)cwv, cwt, s0,
+                       (uint32_t)party, (uint32_t)n_bytes, nlev, force, w->d_pst);
+  };
+  if (!same) {
+    // First call, or changed hints: one call's path — same depth rule, same allocation, a build
+    // that runs whatever the state said.
+    check(1u);
+    HIP_TRY(hipGetLastError());
+    if (int rc = try_prefix(p, c, w, n_bytes, party, cws, cwv, cwt, np1, s0, d, out, st, w->d_pst)) return rc;
+    if (!out->levels) return DCF_OK;  // (h.valid is false: build_prefix cleared it)
+    launch_commit(w, st, 0u, out->levels, 0xFFFFFFFFu, counted * ((2ull << out->levels) - 2));
+    HIP_TRY(hipGetLastError());
+    h = Workspace::PrefixHints{};
+    h.valid = true;
+    h.cwb = cwb;
+    h.s0 = s0;
+    h.party = party;
+    h.n_bytes = n_bytes;
+    h.req = d;
+    h.base = h.depth = out->levels;
+    h.calls = 1;
+    h.epoch = c.epoch;
+    return DCF_OK;
+  }
+  check(0u);
+  HIP_TRY(hipGetLastError());
+  // Deepen (auto depth only: a forced depth keeps the skip of identical rebuilds alone).
+  const uint32_t dmax = (uint32_t)dcf_prefix_reuse_max_depth(n_bytes, p->total_mem, c.prefix_cap);
+  if (c.prefix_levels < 0 && h.grow && h.depth < dmax && h.calls >= dcf_prefix_deepen_calls((int)h.depth, total)) {
+    auto deepen = [&](uint64_t lo, uint64_t hi, uint4* dst) {
+      const unsigned grid = (unsigned)std::min<uint64_t>((hi - lo + kBlock - 1) / kBlock, (uint64_t)p->cus);
+      hipLaunchKernelGGL(k_prefix_deepen16, dim3(grid), dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, h.depth,
+                         lo, hi, (const uint4*)w->d_pfx, dst, p->d_rk0, w->d_pst);
+    };
+    if (((size_t)32 << std::min(h.depth + 2u, dmax)) <= w->pfx_bytes) {
+      // room in the allocation for this level and the next: in place, from the high end
+      // (kernels16.h).  A deepening always leaves room for one more level, so the first one — the
+      // caller has just shown that the key repeats — takes the larger allocation, and the
+      // allocations fall on every other deepening.
+      for (uint32_t j = h.depth; j-- > 0;) deepen(1ull << j, 2ull << j, (uint4*)w->d_pfx);
+      deepen(0, 1, (uint4*)w->d_pfx);
+      launch_commit(w, st, h.depth, h.depth + 1u, 0xFFFFFFFFu, 2ull << h.depth);
+      HIP_TRY(hipGetLastError());
+      ++h.depth;
+      h.calls = 0;
+    } else {
+      // A larger allocation, with room for the level after this one as well (an allocation of this
+      // size and the wait below cost as much as a level saves a call: every other deepening pays
+      // them), else for this level alone.  The old table may still be read by this workspace's
+      // earlier work on other streams, which st waits for: the same discipline as every growth of
+      // d_pfx, but the old buffer lives on until the new rows are written from it.
+      uint8_t* fresh = nullptr;
+      size_t need = 0;
+      for (uint32_t ahead = std::min(h.depth + 2u, dmax); ahead > h.depth && !fresh; --ahead) {
+        need = std::max((size_t)32 << ahead, prefix_table_bytes(p, h.base));
+        if (hipMalloc(&fresh, need) != hipSuccess) {
+          (void)hipGetLastError();  // never fatal
+          fresh = nullptr;
+        }
+      }
+      if (!fresh) {
+        h.grow = false;  // the table stays at this depth
+      } else {
+        deepen(0, 1ull << h.depth, (uint4*)fresh);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) {
+          launch_commit(w, st, h.depth, h.depth + 1u, 0u, 2ull << h.depth);
+          e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+          (void)hipGetLastError();
+          (void)hipStreamSynchronize(st);
+          (void)hipFree(fresh);
+          h.valid = false;
+          return fail(DCF_ERR_HIP, std::string("prefix table deepening: ") + hipGetErrorString(e));
+        }
+        (void)hipFree(w->d_pfx);
+        w->d_pfx = (uint8_t*)fresh;
+        w->pfx_bytes = need;
+        ++h.depth;
+        h.calls = 0;
+      }
+    }
+  }
+  // The key changed under the same pointers (state 0 after the check, or after a deepening that
+  // found another depth than the host expected): rebuild at the first-call depth; else nothing runs.
+  const Workspace::PrefixHints keep = h;  // (build_prefix clears the hints)
+  if (int rc = build_prefix(p, w, n_bytes, party, cws, cwv, cwt, np1, s0, keep.base, out, st, w->d_pst)) return rc;
+  launch_commit(w, st, 0u, keep.base, 0xFFFFFFFFu, counted * ((2ull << keep.base) - 2));
+  HIP_TRY(hipGetLastError());
+  h = keep;
+  ++h.calls;
+  *out = PrefixTable{(const uint4*)w->d_pfx, h.depth};
   return DCF_OK;
 }
 
@@ -880,8 +1070,10 @@ int dcf_hirose_prg_new(const uint8_t* keys, size_t cipher_n, size_t lambda, int 
   for (size_t i = 0; i < cipher_n; i++) aes256_expand_words(keys + 32 * i, &p->rk[i]);
   p->key_blob.assign(keys, keys + 32 * cipher_n);
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) {
     p->cus = prop.multiProcessorCount;
+    p->total_mem = prop.totalGlobalMem;
+  }
   hipError_t e = hipMalloc(&p->d_tab, sizeof(g_tab));
   if (e == hipSuccess) e = hipMemcpy(p->d_tab, g_tab, sizeof(g_tab), hipMemcpyHostToDevice);
   // device copies of the schedules the kernels read per round: cipher 0 (LAMBDA = 16 stream /
@@ -947,7 +1139,7 @@ static void free_workspace(Workspace* w) {
   if (w->aux) (void)hipStreamSynchronize(w->aux);
   if (w->pending) (void)hipEventSynchronize(w->done);  // the last device call's kernels
   for (void* b : {(void*)w->d_ctr, (void*)w->d_ws, (void*)w->d_dig, (void*)w->d_kdig, (void*)w->d_pfx,
-                  (void*)w->d_mkey, (void*)w->d_stage, (void*)w->d_tctr})
+                  (void*)w->d_mkey, (void*)w->d_stage, (void*)w->d_tctr, (void*)w->d_pst})
     if (b) (void)hipFree(b);
   if (w->h_stage) (void)hipHostFree(w->h_stage);
   if (w->h_tiny) (void)hipHostFree(w->h_tiny);
@@ -983,6 +1175,7 @@ int dcf_prg_set_eval_mode(dcf_prg* p, int mode) {
   if (mode != DCF_EVAL_AUTO && mode != DCF_EVAL_TTABLE && mode != DCF_EVAL_STREAM)
     return fail(DCF_ERR_ARG, "bad eval mode (DCF_EVAL_AUTO, DCF_EVAL_TTABLE or DCF_EVAL_STREAM)");
   p->eval_mode = mode;
+  ++p->epoch;  // the cross-call table state starts afresh
   return DCF_OK;
 }
 
@@ -990,6 +1183,7 @@ int dcf_prg_set_prefix_levels(dcf_prg* p, int levels) {
   if (!p) return fail(DCF_ERR_ARG, "null prg");
   if (levels < -1) return fail(DCF_ERR_ARG, "prefix levels must be -1 (auto), 0 (off) or > 0");
   p->prefix_levels = levels;
+  ++p->epoch;  // the cross-call table state starts afresh
   return DCF_OK;
 }
 
@@ -1013,6 +1207,7 @@ int dcf_eval_prefix_levels(const dcf_prg* p, size_t n_bytes, size_t num_keys, si
 int dcf_prg_set_prefix_max_bytes(dcf_prg* p, size_t max_bytes) {
   if (!p) return fail(DCF_ERR_ARG, "null prg");
   p->prefix_cap = max_bytes;
+  ++p->epoch;
   return DCF_OK;
 }
 
@@ -1026,6 +1221,7 @@ size_t dcf_prg_device_bytes(const dcf_prg* p) {
   std::lock_guard<std::mutex> g(const_cast<dcf_prg*>(p)->pool_mu);
   for (const Workspace* w : p->all_ws) {
     if (w->d_ctr) b += kCtrBytes;
+    if (w->d_pst) b += kPfxStateBytes;
     b += (size_t)w->dig_levels * 65 + w->kdig_bytes + w->ws_bytes + w->pfx_bytes +
          w->d_stage_bytes + w->mkey_bytes + w->tctr_bytes;
   }
@@ -1086,6 +1282,7 @@ int dcf_prg_set_phase_timing(dcf_prg* p, int on) {
   if (!p) return fail(DCF_ERR_ARG, "null prg");
   if (on != 0 && on != 1) return fail(DCF_ERR_ARG, "on must be 0 or 1");
   p->timing = on;
+  ++p->epoch;  // a timed call shows a whole call's split: the cross-call table state starts afresh
   return DCF_OK;
 }
 
@@ -1101,6 +1298,15 @@ int dcf_prg_last_eval_phases(dcf_prg* p, float* prep_ms, float* walk_ms, int* pr
   HIP_TRY(hipEventElapsedTime(prep_ms, w->tev[0], w->tev[1]));
   HIP_TRY(hipEventElapsedTime(walk_ms, w->tev[1], w->tev[2]));
   if (prefix_levels) *prefix_levels = (int)w->last_prefix;
+  if (prefix_levels && w->last_prefix_dev && w->d_pst) {  // the depth the walk really read (cross-call table)
+    uint32_t depth = 0;
+    HIP_TRY(hipMemcpy(&depth, w->d_pst, sizeof(depth), hipMemcpyDeviceToHost));
+    *prefix_levels = (int)depth;
+    if (w->ph.valid && depth && depth != w->ph.depth) {  // the key changed in place: the host's guess catches up
+      w->ph.depth = depth;
+      w->ph.calls = 1;
+    }
+  }
   return DCF_OK;
 }
 
@@ -1274,6 +1480,7 @@ static int eval_launch(dcf_prg* p, Lease& L, size_t n_bytes, size_t num_keys, si
   if (!oct_eval(p, L.c, n_bytes, num_keys, (uint64_t)num_keys * ppk))
     HIP_TRY(hipMemsetAsync(L.w->d_ctr, 0, kCtrBytes, L.st));
   L.w->last_prefix = 0;
+  L.w->last_prefix_dev = false;
   phase_mark(p, L, 0);
   const int rc = eval_body(p, L, n_bytes, num_keys, ppk, party, cwb, s0s, xs, ys);
   phase_mark(p, L, 2);
@@ -1423,6 +1630,7 @@ static int eval_body(dcf_prg* p, Lease& L, size_t n_bytes, size_t num_keys, size
     if (multi && c.prefix_levels != 0 && n > kMkPfxLevels && ppk >= 32 && num_keys <= (1ull << (31 - kMkPfxLevels))) {
       // per-key top trees (k_mk_prefix16: 32 rows per key); no room -> walk from the root (same bytes)
       const size_t need = (size_t)num_keys * (32u << kMkPfxLevels);
+      w->ph.valid = false;  // d_pfx changes hands
       if (w->pfx_bytes < need) {
         if (w->d_pfx) {
           HIP_TRY(hipStreamSynchronize(st));
@@ -1485,9 +1693,19 @@ static int eval_body(dcf_prg* p, Lease& L, size_t n_bytes, size_t num_keys, size
       scs = (const uint4*)w->d_kdig;
       sct = w->d_kdig + (size_t)num_keys * n * 32;
     }
+    const uint32_t* pst = nullptr;  // cross-call table: the walk reads its depth here
     if (!multi) {
       const uint32_t d = prefix_depth(p, c, n_bytes, num_keys, total);
-      if (d) {
+      // the cross-call table: dcf_eval_device calls that run a single-key table-start instance
+      if (d && L.reuse && kSkPfx && (n_bytes == 16 || n_bytes == 4) && total < (1ull << 31)) {
+        int rc = reuse_prefix(p, c, w, n_bytes, party, cwb, cws, cwv, cwt, np1, s0s, d, total, &pf, st);
+        if (rc) return rc;
+        w->last_prefix = pf.levels;
+        if (pf.levels) {
+          pst = w->d_pst;
+          w->last_prefix_dev = true;
+        }
+      } else if (d) {
         int rc = try_prefix(p, c, w, n_bytes, party, cws, cwv, cwt, np1, s0s, d, &pf, st);
         if (rc) return rc;
         w->last_prefix = pf.levels;
@@ -1521,7 +1739,7 @@ static int eval_body(dcf_prg* p, Lease& L, size_t n_bytes, size_t num_keys, size
   hipLaunchKernelGGL((k_eval16_stream<NS, XR, MK, PF, NBC, PK2, STG>), dim3((unsigned)blocks), block, 0, st, p->d_tab, \
                      p->rk[0],                                                                                 \
                      lcs, cwv, lct, lnp1, (const uint4*)ls0, (uint32_t)party, lxs, (uint32_t)n_bytes, (uint64_t)kc, \
-                     (uint64_t)ppk, (uint64_t)cnt, w->d_ctr, (uint4*)lys, lpf, p->d_rk0)
+                     (uint64_t)ppk, (uint64_t)cnt, w->d_ctr, (uint4*)lys, lpf, p->d_rk0, pst)
       // multi-key: an instance for "per-key top trees present" (no root-seed start path: 48 -> 33
       // SGPR spills; C5 r03c A/B 414.6 / 413.7 vs 408.5 / 408.1 M evals/s), and of it one with the
       // x width fixed at N = 16 (C5: 33 -> 18 SGPR spills, 121 -> 119 VGPRs, r05k).  Single key, x in
@@ -1587,6 +1805,7 @@ int dcf_eval_device(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, c
   if (m == 0) return DCF_OK;
   DeviceGuard dg(p->device);
   Lease L(p);
+  L.reuse = true;
   if (int rc = L.order((hipStream_t)stream)) return rc;
   return eval_launch(p, L, n_bytes, 1, m, party, cwb, s0, xs, ys);
 }

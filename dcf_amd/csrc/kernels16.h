@@ -630,14 +630,19 @@ __global__ __launch_bounds__(kBlock, 1) void k_mk_prefix16(
 // H > 0: the level-by-level part stops at level D - H (one node or more per thread) and
 // each thread expands its nodes' last H levels depth-first (see the tail below).
 // Round keys per round from the device copy (aes256_tt_gk: SGPR keys spill here).
+// GATED (the cross-call table of dcf_eval_device, PrefixState below): the build runs only when the
+// state word says that no table is valid (0); the word is set afterwards by k_prefix_commit, a
+// kernel of its own, because the workgroups of this grid finish in no fixed order.
 constexpr uint32_t kPfxDfsMax = 4;  // H <= 4: a 3-slot stack of 9-word nodes (27 VGPRs; 5 slots spill to scratch)
+template <bool GATED = false>
 __global__ __launch_bounds__(kBlock, 1) void k_prefix_build16(
     const uint32_t* __restrict__ tab, const RoundKeys rk, const uint4* __restrict__ cw_s,
     const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const uint4* __restrict__ s0,
     const uint32_t party, const uint32_t S, const uint32_t D, const uint32_t H, uint8_t* __restrict__ buf_a,
     uint8_t* __restrict__ buf_b, const uint64_t region_bytes, const uint32_t region_nodes,
-    uint4* __restrict__ table, const uint4* __restrict__ rkg) {
+    uint4* __restrict__ table, const uint4* __restrict__ rkg, const uint32_t* __restrict__ pst) {
   constexpr bool GKB = true;
+  if (GATED && *pst != 0u) return;  // wave-uniform: the table of this key is already there
   __shared__ uint32_t lds[kLdsWords];
   // the narrow levels below the root path: up to 1024 nodes of 32 B (s with t in bit 0 of byte 15 |
   // v); then the depth-first tail's work counter
@@ -873,6 +878,98 @@ __global__ __launch_bounds__(kBlock, 1) void k_prefix_build16(
   __syncthreads();  // (diagnostic builds) stamp when the workgroup's last wave is done
 #endif
   DCF_CLK(7, 1);
+}
+
+// ---- Cross-call shared-prefix table (single key, dcf_eval_device) ----
+// A table stays valid for later calls while everything it was built from stays the same: party,
+// N, s0 and cw_s / cw_v / cw_t of the levels a table can ever cover (kPfxKeyLevels).  Whether it
+// did is decided on the device, byte for byte, against a copy of that material kept beside the
+// table; the host never reads the verdict (no synchronisation), so the build, the deepening and
+// the walk all take the depth from the state word.
+//   state[0]       valid_depth: depth of the table valid for the copied material, 0 = none
+//   state + 4 ...  the material: party (u32) | N (u32) | s0 (16 B) | per level cw_s, cw_v (16 B each), cw_t (1 B)
+constexpr uint32_t kPfxKeyLevels = 31;                         // a table is at most 31 levels deep (one x word)
+constexpr uint32_t kPfxKeyBytes = 24 + 33 * kPfxKeyLevels;     // 1047
+constexpr uint32_t kPfxStateBytes = 2048;                      // state word (16 B slot) + material, rounded up
+
+__device__ __forceinline__ uint8_t pfx_key_byte(uint32_t i, const uint8_t* __restrict__ cw_s,
+                                                const uint8_t* __restrict__ cw_v, const uint8_t* __restrict__ cw_t,
+                                                const uint8_t* __restrict__ s0, uint32_t party, uint32_t nbytes) {
+  if (i < 4u) return (uint8_t)(party >> (8u * i));
+  if (i < 8u) return (uint8_t)(nbytes >> (8u * (i - 4u)));
+  if (i < 24u) return s0[i - 8u];
+  const uint32_t lev = (i - 24u) / 33u, r = (i - 24u) % 33u;
+  return r < 16u ? cw_s[16u * lev + r] : r < 32u ? cw_v[16u * lev + (r - 16u)] : cw_t[lev];
+}
+
+// One workgroup: compare this call's material (levels [0, nlev)) with the copy; on a difference
+// (or `force`: the host starts afresh) the copy is overwritten and valid_depth becomes 0.
+__global__ __launch_bounds__(256) void k_prefix_check(
+    const uint8_t* __restrict__ cw_s, const uint8_t* __restrict__ cw_v, const uint8_t* __restrict__ cw_t,
+    const uint8_t* __restrict__ s0, const uint32_t party, const uint32_t nbytes, const uint32_t nlev,
+    const uint32_t force, uint32_t* __restrict__ state) {
+  __shared__ uint32_t differs;
+  if (threadIdx.x == 0) differs = force;
+  __syncthreads();
+  uint8_t* copy = reinterpret_cast<uint8_t*>(state) + 16;
+  const uint32_t nbytes_key = 24u + 33u * nlev;
+  bool d = false;
+  for (uint32_t i = threadIdx.x; i < nbytes_key; i += blockDim.x)
+    d |= copy[i] != pfx_key_byte(i, cw_s, cw_v, cw_t, s0, party, nbytes);
+  if (d) differs = 1u;
+  __syncthreads();
+  if (!differs) return;
+  for (uint32_t i = threadIdx.x; i < nbytes_key; i += blockDim.x)
+    copy[i] = pfx_key_byte(i, cw_s, cw_v, cw_t, s0, party, nbytes);
+  if (threadIdx.x == 0) state[0] = 0u;
+}
+
+// One thread, after a gated build or a deepening: valid_depth `expect` -> `depth`, and the blocks
+// that step encrypted join the call's block count (ctr[2..3], dcf_prg_last_eval_blocks).  Any other
+// value -> `other` (a build: unchanged, pass expect = 0 and other = ~0; a deepening that did not
+// run leaves rows of no use in the new buffer: other = 0, the gated build that follows rebuilds).
+__global__ void k_prefix_commit(uint32_t* __restrict__ state, uint32_t* __restrict__ ctr, const uint32_t expect,
+                                const uint32_t depth, const uint32_t other, const uint64_t blocks) {
+  const uint32_t cur = state[0];
+  if (cur == expect) {
+    state[0] = depth;
+    reinterpret_cast<unsigned long long*>(ctr)[1] += (unsigned long long)blocks;
+  } else if (other != 0xFFFFFFFFu) {
+    state[0] = other;
+  }
+}
+
+// Deepen a valid table by one level: row i of depth D, for i in [lo, hi), gives rows 2i, 2i + 1 of
+// depth D + 1 with one PRG call (blocks A and B), in the row form of k_prefix_build16's last level.
+// Out of place (dst another buffer): one launch over [0, 2^D).  In place (dst == src, the
+// allocation has room): from the high end, one launch per [2^j, 2^(j+1)), j = D - 1 ... 0, then
+// row 0 — a launch writes [2 lo, 2 hi), above everything it and the later launches read.  Runs
+// only when the state says valid at exactly D (else the key changed under the host's feet).
+__global__ __launch_bounds__(kBlock, 1) void k_prefix_deepen16(
+    const uint32_t* __restrict__ tab, const RoundKeys rk, const uint4* __restrict__ cw_s,
+    const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const uint32_t D, const uint64_t lo,
+    const uint64_t hi, const uint4* src, uint4* dst, const uint4* __restrict__ rkg,
+    const uint32_t* __restrict__ pst) {
+  if (*pst != D) return;  // wave-uniform
+  __shared__ uint32_t lds[kLdsWords];
+  lds_fill_tables(lds, tab);
+  const uint32_t lc = lane_const();
+  const uint4 cs = cw_s[D], cv = cw_v[D];
+  const uint32_t csw[4] = {cs.x, cs.y, cs.z, cs.w}, cvw[4] = {cv.x, cv.y, cv.z, cv.w};
+  const uint32_t ct = cw_t[D];
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += stride) {
+    const uint4 a = src[2u * i], b = src[2u * i + 1u];
+    const uint32_t s[4] = {a.x, a.y, a.z, a.w & kMaskLast}, v[4] = {b.x, b.y, b.z, b.w};
+    const uint32_t t = (a.w >> 24) & 1u;
+    uint32_t sl[4], vl[4], sr[4], vr[4], tl, tr;
+    fd_children<true>(lds, lc, rk, csw, cvw, ct, s, v, t, sl, vl, tl, sr, vr, tr, rkg);
+    uint4* row = dst + 4u * i;
+    row[0] = make_uint4(sl[0], sl[1], sl[2], (sl[3] & kMaskLast) | (tl << 24));
+    row[1] = make_uint4(vl[0], vl[1], vl[2], vl[3]);
+    row[2] = make_uint4(sr[0], sr[1], sr[2], (sr[3] & kMaskLast) | (tr << 24));
+    row[3] = make_uint4(vr[0], vr[1], vr[2], vr[3]);
+  }
 }
 
 // Last H levels of the full-domain expansion depth-first (as k_prefix_build16's tail): one

@@ -738,10 +738,16 @@ __global__ __launch_bounds__(kBlock, 1) void k_eval16_stream(
     const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const uint4* __restrict__ cw_np1,
     const uint4* __restrict__ s0s, const uint32_t party, const uint8_t* __restrict__ xs, const uint32_t nbytes,
     const uint64_t num_keys, const uint64_t ppk, const uint64_t total, uint32_t* __restrict__ ctr,
-    uint4* __restrict__ ys, const PrefixTable pf, const uint4* __restrict__ rkg) {
+    uint4* __restrict__ ys, const PrefixTable pf_arg, const uint4* __restrict__ rkg,
+    const uint32_t* __restrict__ pst) {
   __shared__ uint32_t lds[kLdsWords];
   lds_fill_tables(lds, tab);
   DCF_CLK(2, 0);
+  // Single key below the cross-call table (kernels16.h PrefixState): the depth is whatever the
+  // device state says is valid, not what the host guessed — one scalar load per wave, ahead of the loop.
+  PrefixTable pf = pf_arg;
+  if constexpr (PFX && !MULTI)
+    if (pst) pf.levels = __builtin_amdgcn_readfirstlane(*pst);
   // Round keys: per round from the device copy (GK), except in the multi-key instances with per-key
   // top trees (C5), which keep them in SGPRs (device-copy keys cost C5 14 %, AB_LOG).  The multi-key
   // instance without top trees (fewer than 32 points per key, or prefix levels forced off) has the

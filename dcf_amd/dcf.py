@@ -197,9 +197,20 @@ class Aes256HirosePrg:
             check(r)
         return r
 
+    @staticmethod
+    def prefix_deepen_calls(depth: int, points: int) -> int:
+        """Calls of `points` points after which the cross-call table is deepened from `depth`."""
+        return int(_lib.load().dcf_prefix_deepen_calls(int(depth), int(points)))
+
+    @staticmethod
+    def prefix_reuse_max_depth(n_bytes: int, device_bytes: int, cap_bytes: int = 0) -> int:
+        """The deepest table the cross-call reuse grows to (include/dcf_hip.h)."""
+        return int(_lib.load().dcf_prefix_reuse_max_depth(int(n_bytes), int(device_bytes), int(cap_bytes)))
+
     def last_eval_blocks(self) -> int:
         """AES blocks the last stream-engine eval encrypted for live points, counted on the
-        device (no prefix table build).  Call after synchronizing the eval's stream."""
+        device (no prefix table build, except eval_device's cross-call table at automatic depth:
+        the build or deepening that really ran in the call).  Call after synchronizing the eval's stream."""
         n = ctypes.c_uint64(0)
         check(_lib.load().dcf_prg_last_eval_blocks(self._h, ctypes.byref(n)))
         return int(n.value)

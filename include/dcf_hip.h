@@ -169,6 +169,35 @@ size_t dcf_eval_keys_per_launch(size_t n_bytes, size_t points_per_key);
  * (the default: 4.85e9 B at the auto cap D = 27, Hirose LAMBDA = 16).  Forced depths ignore
  * it.  Output bytes never change. */
 int dcf_prg_set_prefix_max_bytes(dcf_prg* prg, size_t max_bytes);
+
+/* Cross-call shared-prefix table.  dcf_eval_device calls with one key, LAMBDA = 16, the Hirose
+ * PRG and N = 16 or N = 4 on the stream engine keep their table on the prg (per workspace) after
+ * the call.  The next such call with the same cwb / s0 pointers, party, N and point-count class
+ * compares, on the device and byte for byte, the key material a table is built from (party, N,
+ * s0, cw_s / cw_v / cw_t of levels [0, min(31, 8N - 1))) with a copy kept beside the table:
+ *   - equal: no rebuild.  At automatic depth the table is also deepened by one level at the start
+ *     of a call once dcf_prefix_deepen_calls(D, m) calls have walked at depth D, up to
+ *     dcf_prefix_reuse_max_depth(N, device memory, dcf_prg_set_prefix_max_bytes cap); a failed
+ *     allocation keeps the depth.  A forced depth (dcf_prg_set_prefix_levels(k > 0)) is never deepened.
+ *   - different (the key buffer was rewritten in place): the table is rebuilt at the first call's
+ *     depth inside the same call.  Correction words of deeper levels and cw_np1 are not table
+ *     material and may change freely.
+ * The call stays asynchronous (no host read of the verdict); a call that deepens waits for its
+ * stream once, to free the smaller table.  Output bytes never change.  dcf_prg_set_prefix_levels,
+ * dcf_prg_set_eval_mode, dcf_prg_set_prefix_max_bytes and dcf_prg_set_phase_timing (so that a
+ * timed call shows a whole call's table / walk split) make the next call start afresh;
+ * dcf_prg_trim / dcf_prg_free release the table.  Other entry points (host pointers, multi-key,
+ * range, full domain, multi-GPU) build their tables per call as before.
+ *
+ * dcf_prefix_deepen_calls: calls of m points after which deepening D -> D + 1 has paid for
+ * itself, ceil(2^(D+1) / (1.257 m)) (2^(D+1) blocks once against 1.257 m per call), at least 1;
+ * 0 = never (D outside [0, 31), m = 0).  m = 2^28: 1 at D = 27, 2 at 28, 4 at 29, 7 at 30.
+ * dcf_prefix_reuse_max_depth: the deepest table reuse may grow to: min(31, 8N - 1), lowered until
+ * the table's 32 * 2^D bytes fit 1/8 of device_bytes, and what a one-call build of that depth
+ * takes (the sizes listed at dcf_prg_set_prefix_levels) fits cap_bytes (0 = no cap).
+ * Both are pure arithmetic (no device access). */
+uint64_t dcf_prefix_deepen_calls(int depth, size_t points);
+int dcf_prefix_reuse_max_depth(size_t n_bytes, size_t device_bytes, size_t cap_bytes);
 /* Device memory this dcf_prg currently holds (tables, prefix tables, scratch, staging, over
  * all of its workspaces). */
 size_t dcf_prg_device_bytes(const dcf_prg* prg);
@@ -188,7 +217,10 @@ int dcf_prg_trim(dcf_prg* prg);
  * encrypted for live points (LAMBDA = 16: the DCF_EVAL_STREAM engine;
  * LAMBDA >= 32: the stream head over all of the call's keys and passes; not counting a
  * shared-prefix table build, except the multi-key per-key top trees, whose blocks are
- * included), counted on the device; 0 for engines that do not count.
+ * included, and the cross-call table of dcf_eval_device (above) at automatic depth: there the
+ * count includes the blocks of the build (2^(D+1) - 2) or deepening (2^(D+1)) that really ran in
+ * this call, decided on the device — none on a call that reused the table; at a forced depth the
+ * walk alone), counted on the device; 0 for engines that do not count.
  * Measurement hook for the bench; call after the eval's stream has been synchronized.  0
  * before any eval; DCF_ERR_ARG while that call's workspace is leased by another call (the
  * hook never reads a workspace in use). */
@@ -199,7 +231,9 @@ int dcf_prg_last_eval_blocks(dcf_prg* prg, uint64_t* blocks);
  * prefix table, per-key top trees or CW digest/rows were built) and at the end.
  * dcf_prg_last_eval_phases reads the last eval call's split (call after synchronizing its
  * stream): prep_ms = table / digest preparation, walk_ms = the walk kernels, prefix_levels =
- * the shared-prefix depth it used (0 = none).  DCF_ERR_ARG if no timed eval has run, or while
+ * the shared-prefix depth it used (0 = none; for the cross-call table of dcf_eval_device the
+ * depth the walk read from the device state, which after an in-place key change is the first
+ * call's depth again).  DCF_ERR_ARG if no timed eval has run, or while
  * that call's workspace is leased by another call. */
 int dcf_prg_set_phase_timing(dcf_prg* prg, int on);
 int dcf_prg_last_eval_phases(dcf_prg* prg, float* prep_ms, float* walk_ms, int* prefix_levels);

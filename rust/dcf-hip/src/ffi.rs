@@ -33,6 +33,8 @@ extern "C" {
     pub fn dcf_eval_prefix_levels(prg: *const DcfPrg, n_bytes: usize, num_keys: usize, points_per_key: usize) -> c_int;
     pub fn dcf_eval_keys_per_launch(n_bytes: usize, points_per_key: usize) -> usize;
     pub fn dcf_prg_set_prefix_max_bytes(prg: *mut DcfPrg, max_bytes: usize) -> c_int;
+    pub fn dcf_prefix_deepen_calls(depth: c_int, points: usize) -> u64;
+    pub fn dcf_prefix_reuse_max_depth(n_bytes: usize, device_bytes: usize, cap_bytes: usize) -> c_int;
     pub fn dcf_prg_device_bytes(prg: *const DcfPrg) -> usize;
     pub fn dcf_prg_host_pinned_bytes(prg: *const DcfPrg) -> usize;
     pub fn dcf_prg_workspaces(prg: *const DcfPrg) -> c_int;

@@ -371,33 +371,37 @@ uint32_t capped_depth(const dcf_prg* p, const Cfg& c, uint32_t d) {
   return d >= 8u ? d : 0u;
 }
 
-uint32_t prefix_depth(const dcf_prg* p, const Cfg& c, size_t n_bytes, uint64_t num_keys, uint64_t total) {
-  if (p->lambda != 16 || num_keys != 1 || c.prefix_levels == 0) return 0;
-  uint32_t d;
-  if (c.prefix_levels > 0) {
-    d = std::min((uint32_t)c.prefix_levels, kPrefixMaxForced);
-  } else {
-    // Hirose (one-launch build, k_prefix_build16): D = log2(total), r02g sweep C2 (2^24
-    // points) D = 22/23/24/25 -> 3.97/4.08/4.13/3.93 G evals/s; MMO (level kernels): log2 - 1
-    const uint32_t lg = 63u - (uint32_t)__builtin_clzll(total | 1u);
-    d = p->kind == 0 ? lg : (lg > 1u ? lg - 1u : 0u);
-    if (d < 8u) return 0;
-    d = std::min(d, kPrefixMax);
-    d = capped_depth(p, c, std::min<uint32_t>(d, (uint32_t)(8 * n_bytes - 1)));
-  }
-  return std::min<uint32_t>(d, (uint32_t)(8 * n_bytes - 1));
+// The forced depth (at most max_forced), else the automatic depth d (none below 8, at most
+// max_auto, under the cap); always < 8N.
+uint32_t depth_rule(const dcf_prg* p, const Cfg& c, size_t n_bytes, uint32_t d, uint32_t max_auto, uint32_t max_forced) {
+  const uint32_t top = (uint32_t)(8 * n_bytes - 1);
+  if (c.prefix_levels > 0) return std::min(std::min((uint32_t)c.prefix_levels, max_forced), top);
+  if (d < 8u) return 0;
+  return std::min(capped_depth(p, c, std::min(std::min(d, max_auto), top)), top);
 }
 
-// Tiny batches run the latency kernels of kernels_lat.h (thresholds below and at kEvalRowMax).
+uint32_t prefix_depth(const dcf_prg* p, const Cfg& c, size_t n_bytes, uint64_t num_keys, uint64_t total) {
+  if (p->lambda != 16 || num_keys != 1 || c.prefix_levels == 0) return 0;
+  // Hirose (one-launch build, k_prefix_build16): D = log2(total), r02g sweep C2 (2^24
+  // points) D = 22/23/24/25 -> 3.97/4.08/4.13/3.93 G evals/s; MMO (level kernels): log2 - 1
+  const uint32_t lg = 63u - (uint32_t)__builtin_clzll(total | 1u);
+  return depth_rule(p, c, n_bytes, p->kind == 0 ? lg : (lg > 1u ? lg - 1u : 0u), kPrefixMax, kPrefixMaxForced);
+}
+
+// Tiny batches run the latency kernels of kernels_lat.h (one AES column per lane).  Thresholds:
+// scripts/lat_sweep.py / row_threshold.py (DESIGN.md §4 "Latency kernels", profiles/AB_LOG.md).
 #ifndef DCF_EVAL_OCT_MAX
 #define DCF_EVAL_OCT_MAX 32768
 #endif
 constexpr uint64_t kEvalOctMax = DCF_EVAL_OCT_MAX;  // points (one key) up to which auto-mode eval runs k_eval16_oct
                                          // (r03a, us per device call: 32768 oct 187 vs pair 273; 100k 623 vs 485)
-bool oct_eval(const dcf_prg* p, const Cfg& c, size_t n_bytes, uint64_t num_keys, uint64_t total) {
-  return p->kind == 0 && p->lambda == 16 && num_keys == 1 && total <= kEvalOctMax && 8 * n_bytes <= kColMaxLevels &&
-         c.prefix_levels <= 0 && c.mode == DCF_EVAL_AUTO;
-}
+constexpr uint64_t kEvalRowMax = 8192;   // points up to which auto-mode eval runs k_eval16_row (32 lanes per point)
+#ifndef DCF_EVAL_ROW2_MAX
+#define DCF_EVAL_ROW2_MAX 2048
+#endif
+constexpr uint64_t kEvalRow2Max = DCF_EVAL_ROW2_MAX;  // ... k_eval16_row2 (64 lanes per point, two levels per
+// chain on right steps) up to this many points (r06i, us per device call, row2 vs row: 1 point 75.7 vs
+// 97.6, 256 81.9 vs 108.1, 2048 87.4 vs 97.7, 4096 105.1 vs 100.3)
 
 // Shared-prefix depth for the small-batch pair path (k_eval16_pair: one key, fewer points than
 // two per lane of the GPU, more than the latency kernels take).  Forced: dcf_prg_set_prefix_levels.
@@ -428,17 +432,79 @@ uint32_t small_prefix_depth(const dcf_prg* p, const Cfg& c, size_t n_bytes, uint
 constexpr uint32_t kWidePrefixMax = 22;
 uint32_t wide_prefix_depth(const dcf_prg* p, const Cfg& c, size_t n_bytes, uint64_t m) {
   if (p->lambda <= 16 || p->kind != 0 || c.prefix_levels == 0 || m == 0) return 0;
-  uint32_t d;
-  if (c.prefix_levels > 0) {
-    d = std::min((uint32_t)c.prefix_levels, 30u);
-  } else {
-    const uint32_t lg = 63u - (uint32_t)__builtin_clzll(m | 1u);
-    d = lg > 1u ? lg - 1u : 0u;
-    if (d < 8u) return 0;
-    d = std::min(d, kWidePrefixMax);
-    d = capped_depth(p, c, std::min<uint32_t>(d, (uint32_t)(8 * n_bytes - 1)));
+  const uint32_t lg = 63u - (uint32_t)__builtin_clzll(m | 1u);
+  return depth_rule(p, c, n_bytes, lg > 1u ? lg - 1u : 0u, kWidePrefixMax, 30u);
+}
+
+// The multi-key shapes eval_wide_batch takes: several keys of few points each (larger keys amortise their own
+// launches: eval_wide per key), Hirose PRG, no forced prefix depth (that runs the per-key passes, a table each).
+constexpr uint64_t kWideBatchPpk = 32768;
+bool wide_batched(const dcf_prg* p, const Cfg& c, uint64_t num_keys, uint64_t ppk) {
+  return num_keys > 1 && ppk > 0 && p->kind == 0 && ppk <= kWideBatchPpk && c.prefix_levels <= 0;
+}
+
+// ---- One plan per eval call: plan_eval() alone tests the eval path's thresholds;
+// eval_launch, eval_body, host_eval and dcf_eval_prefix_levels read the plan ----
+enum class Engine {
+  WideBatch, WidePerKey,  // LAMBDA >= 32: eval_wide_batch / eval_wide or eval_mmo_wide key by key
+  Mmo16,                  // k_eval16_mmo, whatever the engine setting
+  Row2, Row, Oct,         // the latency kernels (kernels_lat.h)
+  Pair, Stream, TTable,   // k_eval16_pair / k_eval16_stream / k_eval16
+};
+struct EvalPlan {
+  Engine engine = Engine::TTable;
+  // The one-call shared-prefix depth asked for (what dcf_eval_prefix_levels returns), 0 where the
+  // engine builds no shared table; the multi-key stream engine's top trees (kMkPfxLevels) are none.
+  uint32_t depth = 0;
+  int key_mode = 0;    // how a lockstep kernel finds a point's key: 0 one key, 1 ppk % 64 == 0, 2 any
+  // LAMBDA = 16, auto mode, fewer points than two per lane of the GPU: set whatever the engine (MMO and the
+  // latency kernels too, not only Pair); beyond plan_eval only host_eval's mid path reads it
+  bool small = false;
+  const char* unsupported = nullptr;  // why eval_body fails the call (DCF_ERR_UNSUPPORTED), before any device work
+  // a latency kernel: it zeroes d_ctr itself, and a host call passes through the mapped tiny buffer
+  bool latency() const { return engine == Engine::Row2 || engine == Engine::Row || engine == Engine::Oct; }
+};
+
+EvalPlan plan_eval(const dcf_prg* p, const Cfg& c, size_t n_bytes, uint64_t num_keys, uint64_t ppk) {
+  EvalPlan pl;
+  const uint64_t total = num_keys * ppk;
+  const bool few = total < (uint64_t)p->cus * kBlock * 2;
+  pl.key_mode = num_keys == 1 ? 0 : ppk % 64 == 0 ? 1 : 2;
+  pl.small = p->lambda == 16 && c.mode == DCF_EVAL_AUTO && few;
+  if (p->lambda > 16) {  // batched keys build no table; per-key passes do (Hirose only)
+    pl.engine = wide_batched(p, c, num_keys, ppk) ? Engine::WideBatch : Engine::WidePerKey;
+    if (pl.engine == Engine::WidePerKey) pl.depth = wide_prefix_depth(p, c, n_bytes, ppk);
+    return pl;
   }
-  return std::min<uint32_t>(d, (uint32_t)(8 * n_bytes - 1));
+  if (p->kind == 1) {  // one key (prefix_depth); auto depth: none for small batches (latency-bound:
+    pl.engine = Engine::Mmo16;  // the table's D launches cost what it saves)
+    if (c.prefix_levels > 0 || !few) pl.depth = prefix_depth(p, c, n_bytes, num_keys, total);
+    return pl;
+  }
+  if (c.mode == DCF_EVAL_AUTO && num_keys == 1 && total <= kEvalOctMax && 8 * n_bytes <= kColMaxLevels &&
+      c.prefix_levels <= 0) {
+    pl.engine = total <= kEvalRow2Max ? Engine::Row2 : total <= kEvalRowMax ? Engine::Row : Engine::Oct;
+    return pl;
+  }
+  // Auto: small batches (fewer points than two per lane of the GPU) are latency-bound: one
+  // point's 8N levels run back to back, so the lockstep walk (A and B of a level in one AES
+  // pass: 8N passes) beats the stream engine (~12N passes); it runs on a lane pair per point
+  // (k_eval16_pair: the even lane encrypts A, the odd lane B), spread over every CU with
+  // workgroups just big enough (C1).  Larger batches: the stream engine, single key or many
+  // (C3 r01: 407 M evals/s vs 332 M lockstep T-table; C5 with the key-major digest).  DCF_EVAL_TTABLE
+  // forces the lockstep walk (k_eval16: A and B every level), which auto takes for many keys at N > 32.
+  if (pl.small) {
+    pl.engine = Engine::Pair;
+    if (num_keys == 1) pl.depth = small_prefix_depth(p, c, n_bytes, total);
+    return pl;
+  }
+  const bool stream = c.mode == DCF_EVAL_STREAM || (c.mode == DCF_EVAL_AUTO && (num_keys == 1 || n_bytes <= 32));
+  pl.engine = stream ? Engine::Stream : Engine::TTable;
+  if (stream && num_keys > 1 && n_bytes > 32) pl.unsupported = "multi-key stream eval: N <= 32";
+  else if (stream && num_keys > 1 && ppk >= (1ull << 31)) pl.unsupported = "multi-key stream eval: 2^31 points per key or more";
+  else if (stream) pl.depth = prefix_depth(p, c, n_bytes, num_keys, total);  // (one key only)
+  else if ((total + 63) / 64 > 0xFFFFFFFFull) pl.unsupported = "more than 2^32 64-point units";
+  return pl;
 }
 
 // Expand the top `levels` levels of one key's tree for the wide stream head (the CW
@@ -456,23 +522,38 @@ int build_wide_prefix(dcf_prg* p, Workspace* w, uint32_t nlev, int party, const 
   uint4* table = (uint4*)w->d_pfx;
   uint4* ba = (uint4*)(w->d_pfx + tab_bytes);
   uint4* bb = (uint4*)(w->d_pfx + tab_bytes + ((size_t)1 << S) * region);
-  if (p->lambda == 32)
-    hipLaunchKernelGGL(k_wpfx_build<true>, dim3(1u << S), dim3(kBlock), 0, st, p->d_tab, p->d_rk2,
-                       (const uint4*)w->d_dig, w->d_dig + (size_t)nlev * 64, s0, (uint32_t)party, S, levels, ba, bb, R,
-                       table);
-  else
-    hipLaunchKernelGGL(k_wpfx_build<false>, dim3(1u << S), dim3(kBlock), 0, st, p->d_tab, p->d_rk2,
-                       (const uint4*)w->d_dig, w->d_dig + (size_t)nlev * 64, s0, (uint32_t)party, S, levels, ba, bb, R,
-                       table);
+  hipLaunchKernelGGL(p->lambda == 32 ? k_wpfx_build<true> : k_wpfx_build<false>, dim3(1u << S), dim3(kBlock), 0, st,
+                     p->d_tab, p->d_rk2, (const uint4*)w->d_dig, w->d_dig + (size_t)nlev * 64, s0, (uint32_t)party, S,
+                     levels, ba, bb, R, table);
   HIP_TRY(hipGetLastError());
   *out = WidePrefix{table, levels};
   return DCF_OK;
 }
 
+// Make w->d_pfx at least `need` bytes (contents not kept; the caller has cleared w->ph.valid).
+// Unlike grow(), a failed allocation does not fail the call: *oom holds its error, d_pfx is
+// empty, and the caller walks with a shallower table or none.
+int reserve_pfx(Workspace* w, size_t need, hipStream_t st, hipError_t* oom) {
+  *oom = hipSuccess;
+  if (w->pfx_bytes >= need) return DCF_OK;
+  if (w->d_pfx) {
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipFree(w->d_pfx));
+    w->d_pfx = nullptr;
+    w->pfx_bytes = 0;
+  }
+  *oom = hipMalloc(&w->d_pfx, need);
+  if (*oom == hipSuccess) {
+    w->pfx_bytes = need;
+  } else {
+    (void)hipGetLastError();
+    w->d_pfx = nullptr;
+  }
+  return DCF_OK;
+}
 
 // Expand the top `levels` levels of the key's tree (s = s0, v = 0, t = party at the
 // root; k_fd_level16 per level, as the full-domain eval does) into w->d_pfx.
-
 // pst (reuse_prefix, Hirose only): the gated build, which runs only if the device state word says
 // that no table is valid; reuse_prefix sets the hints again afterwards.
 int build_prefix(dcf_prg* p, Workspace* w, size_t n_bytes, int party, const uint4* cws, const uint4* cwv,
@@ -487,37 +568,20 @@ int build_prefix(dcf_prg* p, Workspace* w, size_t n_bytes, int party, const uint
   const size_t region = ((size_t)R * nodeb + 255) & ~(size_t)255;
   const size_t tab_bytes = (maxnodes * 32 + 255) & ~(size_t)255;
   const size_t need = p->kind == 0 ? tab_bytes + 2 * ((size_t)1 << S) * region : 2 * half + 64 * sizeof(uint32_t);
-  if (w->pfx_bytes < need) {
-    if (w->d_pfx) {
-      HIP_TRY(hipStreamSynchronize(st));
-      HIP_TRY(hipFree(w->d_pfx));
-      w->d_pfx = nullptr;
-      w->pfx_bytes = 0;
-    }
-    const hipError_t e = hipMalloc(&w->d_pfx, need);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      w->d_pfx = nullptr;
-      return fail(kPrefixNoMem, std::string("prefix table: hipMalloc: ") + hipGetErrorString(e));
-    }
-    w->pfx_bytes = need;
-  }
-  if (p->kind == 0) {  // one launch: k_prefix_build16
+  hipError_t oom;
+  if (int rc = reserve_pfx(w, need, st, &oom)) return rc;
+  if (oom != hipSuccess) return fail(kPrefixNoMem, std::string("prefix table: hipMalloc: ") + hipGetErrorString(oom));
+  if (p->kind == 0) {  // one launch: k_prefix_build16 (gated by the state word where there is one)
     uint8_t* ba = w->d_pfx + tab_bytes;
     const uint32_t H = prefix_dfs_levels(levels, S);
-    if (pst)
-      hipLaunchKernelGGL(k_prefix_build16<true>, dim3(1u << S), dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt,
-                         (const uint4*)s0, (uint32_t)party, S, levels, H, ba, ba + ((size_t)1 << S) * region,
-                         (uint64_t)region, R, (uint4*)w->d_pfx, p->d_rk0, pst);
-    else
-      hipLaunchKernelGGL(k_prefix_build16<false>, dim3(1u << S), dim3(kBlock), 0, st, p->d_tab, p->rk[0], cws, cwv, cwt,
-                         (const uint4*)s0, (uint32_t)party, S, levels, H, ba, ba + ((size_t)1 << S) * region,
-                         (uint64_t)region, R, (uint4*)w->d_pfx, p->d_rk0, (const uint32_t*)nullptr);
+    hipLaunchKernelGGL(pst ? k_prefix_build16<true> : k_prefix_build16<false>, dim3(1u << S), dim3(kBlock), 0, st,
+                       p->d_tab, p->rk[0], cws, cwv, cwt, (const uint4*)s0, (uint32_t)party, S, levels, H, ba,
+                       ba + ((size_t)1 << S) * region, (uint64_t)region, R, (uint4*)w->d_pfx, p->d_rk0, pst);
     HIP_TRY(hipGetLastError());
     *out = PrefixTable{(const uint4*)w->d_pfx, levels};
     return DCF_OK;
   }
-  uint4* s_a = (uint4*)w->d_pfx;
+  uint4* s_a = (uint4*)w->d_pfx;  // MMO (the Hirose PRG returned above): a launch per level
   uint4* v_a = s_a + maxnodes;
   uint8_t* t_a = (uint8_t*)(v_a + maxnodes);
   uint4* s_b = (uint4*)(w->d_pfx + half);
@@ -530,14 +594,9 @@ int build_prefix(dcf_prg* p, Workspace* w, size_t n_bytes, int party, const uint
   const uint32_t nlev = (uint32_t)(8 * n_bytes);  // > levels: no level here is the last one
   for (uint32_t lev = 0; lev < levels; ++lev) {
     const uint64_t parents = 1ull << lev;
-    if (p->kind == 1)
-      hipLaunchKernelGGL(k_fd_level16_mmo, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
-                         p->d_rk128, cws, cwv, cwt, np1, lev, nlev, parents, s_a, v_a, t_a, s_b, v_b, t_b,
-                         (uint4*)nullptr, ctrs + lev);
-    else
-      hipLaunchKernelGGL(k_fd_level16, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
-                         p->rk[0], cws, cwv, cwt, np1, lev, nlev, parents, s_a, v_a, t_a, s_b, v_b, t_b,
-                         (uint4*)nullptr, ctrs + lev);
+    hipLaunchKernelGGL(k_fd_level16_mmo, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
+                       p->d_rk128, cws, cwv, cwt, np1, lev, nlev, parents, s_a, v_a, t_a, s_b, v_b, t_b,
+                       (uint4*)nullptr, ctrs + lev);
     HIP_TRY(hipGetLastError());
     std::swap(s_a, s_b);
     std::swap(v_a, v_b);
@@ -553,12 +612,14 @@ int build_prefix(dcf_prg* p, Workspace* w, size_t n_bytes, int party, const uint
 
 // build_prefix at depth d; in auto mode (prefix_levels < 0) an allocation failure retries
 // two levels shallower, down to 8, and then evaluates without a table (same output bytes).
+// d = 0: no table.  The depth built goes to w->last_prefix.
 int try_prefix(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, int party, const uint4* cws, const uint4* cwv,
                const uint8_t* cwt, const uint4* np1, const uint8_t* s0, uint32_t d, PrefixTable* out, hipStream_t st,
                const uint32_t* pst = nullptr) {
   *out = PrefixTable{nullptr, 0u};
   while (d) {
     const int rc = build_prefix(p, w, n_bytes, party, cws, cwv, cwt, np1, s0, d, out, st, pst);
+    if (rc == DCF_OK) w->last_prefix = out->levels;
     if (rc != kPrefixNoMem) return rc;
     if (c.prefix_levels >= 0) return fail(DCF_ERR_HIP, t_err);  // a forced depth must fit
     d = d >= 10u ? d - 2u : 0u;
@@ -849,7 +910,8 @@ int run_tail(const uint8_t* cws, const uint8_t* cwv, const uint8_t* np1, const u
 
 // Dcf::eval at LAMBDA >= 32 for key `key` of a K-key CWB (see kernels_wide.h).
 // The caller (eval_launch) has zeroed the workspace's block count once for the whole call.
-int eval_wide(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, uint64_t K, uint64_t key, int party, const uint8_t* cwb,
+// d: the shared-prefix depth of the call's plan (wide_prefix_depth), 0 for none.
+int eval_wide(dcf_prg* p, uint32_t d, Workspace* w, size_t n_bytes, uint64_t K, uint64_t key, int party, const uint8_t* cwb,
               const uint8_t* s0, const uint8_t* xs, uint64_t m, uint8_t* ys, hipStream_t st) {
   const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * n_bytes);
   const size_t n = 8 * n_bytes;
@@ -878,7 +940,6 @@ int eval_wide(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, uint64_t K
         hipLaunchKernelGGL(k_cw_digest, dim3((4 * nlev + 255) / 256), dim3(256), 0, st, cws, cwv, cwt, nlev, lam, K,
                            key, 1u, (uint4*)w->d_dig, w->d_dig + (size_t)nlev * 64);
         HIP_TRY(hipGetLastError());
-        const uint32_t d = wide_prefix_depth(p, c, n_bytes, m);
         if (d) {
           rc = build_wide_prefix(p, w, nlev, party, s0, d, &wpf, st);
           if (rc) return rc;
@@ -911,16 +972,10 @@ int eval_wide(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, uint64_t K
 
 // Dcf::eval at LAMBDA >= 32 for keys 0 .. K - 1, ppk points each (key-major xs / ys, s0s[K][LAMBDA]),
 // several keys per pass: one key-major CW digest, one stream-head launch (each point's key =
-// point / ppk) and one tail launch whose workgroups build the tables of their own key.  For
-// ppk <= kWideBatchPpk (larger keys amortise their own launches: eval_wide per key).  No shared
-// prefix; the MMO PRG keeps the per-key path.
-constexpr uint64_t kWideBatchPpk = 32768;
+// point / ppk) and one tail launch whose workgroups build the tables of their own key.  For the
+// shapes of wide_batched() (ppk <= kWideBatchPpk).  No shared prefix; the MMO PRG keeps the
+// per-key path.
 constexpr uint64_t kWideBatchKeys = 4096;  // keys per pass: tail grid rows (keys x <= 8 ranges) <= 32768
-// The multi-key shapes eval_wide_batch takes: several keys of few points each, Hirose PRG, and no
-// forced prefix depth (a forced depth runs the per-key passes, which build one table per key).
-bool wide_batched(const dcf_prg* p, const Cfg& c, uint64_t num_keys, uint64_t ppk) {
-  return num_keys > 1 && ppk > 0 && p->kind == 0 && ppk <= kWideBatchPpk && c.prefix_levels <= 0;
-}
 
 int eval_wide_batch(dcf_prg* p, Workspace* w, size_t n_bytes, uint64_t K, uint64_t ppk, int party,
                     const uint8_t* cwb, const uint8_t* s0s, const uint8_t* xs, uint8_t* ys, hipStream_t st) {
@@ -1190,18 +1245,7 @@ int dcf_prg_set_prefix_levels(dcf_prg* p, int levels) {
 int dcf_eval_prefix_levels(const dcf_prg* p, size_t n_bytes, size_t num_keys, size_t points_per_key) {
   if (!p) return fail(DCF_ERR_ARG, "null prg");
   if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
-  const uint64_t total = (uint64_t)num_keys * points_per_key;
-  // the paths eval_launch takes without a table: small batches (MMO: at auto depth; Hirose: in
-  // auto mode), Hirose engines other than the stream engine (MMO ignores the engine setting)
-  const Cfg c = snapshot(p);
-  const bool small = total < (uint64_t)p->cus * kBlock * 2;
-  if (p->kind == 1 && p->lambda > 16) return 0;  // MMO at LAMBDA >= 32: no shared prefix (head/tail per block)
-  if (p->kind == 1) return small && c.prefix_levels < 0 ? 0 : (int)prefix_depth(p, c, n_bytes, num_keys, total);
-  if (p->lambda > 16)  // batched keys (eval_wide_batch) build no table; per-key passes do
-    return wide_batched(p, c, num_keys, points_per_key) ? 0 : (int)wide_prefix_depth(p, c, n_bytes, points_per_key);
-  if (c.mode == DCF_EVAL_AUTO && small) return num_keys == 1 ? (int)small_prefix_depth(p, c, n_bytes, total) : 0;
-  if (c.mode != DCF_EVAL_AUTO && c.mode != DCF_EVAL_STREAM) return 0;
-  return (int)prefix_depth(p, c, n_bytes, num_keys, total);
+  return (int)plan_eval(p, snapshot(p), n_bytes, num_keys, points_per_key).depth;
 }
 
 int dcf_prg_set_prefix_max_bytes(dcf_prg* p, size_t max_bytes) {
@@ -1325,15 +1369,7 @@ int dcf_prg_trim(dcf_prg* p) {
   return (int)idle.size();
 }
 
-// Tiny batches run the latency kernels of kernels_lat.h (one AES column per lane).  Thresholds:
-// scripts/lat_sweep.py / row_threshold.py (DESIGN.md §4 "Latency kernels", profiles/AB_LOG.md).
-constexpr uint64_t kEvalRowMax = 8192;   // points up to which auto-mode eval runs k_eval16_row (32 lanes per point)
-#ifndef DCF_EVAL_ROW2_MAX
-#define DCF_EVAL_ROW2_MAX 2048
-#endif
-constexpr uint64_t kEvalRow2Max = DCF_EVAL_ROW2_MAX;  // ... k_eval16_row2 (64 lanes per point, two levels per
-// chain on right steps) up to this many points (r06i, us per device call, row2 vs row: 1 point 75.7 vs
-// 97.6, 256 81.9 vs 108.1, 2048 87.4 vs 97.7, 4096 105.1 vs 100.3)
+// Small gen batches run the latency kernels of kernels_lat.h as well (eval's thresholds: plan_eval).
 constexpr uint64_t kGenRowMax = 2048;    // keys up to which gen runs k_gen16_row (one wave per key; pipelined, r03t3:
                                          // 2048 keys 110 vs 148 us col, 4096 keys 149 vs 147, 8192 277 vs 165)
 constexpr uint64_t kGenColMax = 16384;   // keys up to which gen runs k_gen16_col (r03a: 4096 keys 232 vs 562 us quads)
@@ -1436,12 +1472,7 @@ int dcf_gen_batch_device(dcf_prg* p, size_t n_bytes, size_t num_keys, const uint
   return gen_launch(p, L, n_bytes, num_keys, alpha, beta, s0_0, s0_1, bound, cwb_out);
 }
 
-// Dcf::eval of K keys x ppk points on the lease's stream (arguments checked by the caller).
-// Phase marks (dcf_prg_set_phase_timing): 0 at entry, 1 before the walk kernel (after any
-// table / digest preparation), 2 at the end.
-static int eval_body(dcf_prg* p, Lease& L, size_t n_bytes, size_t num_keys, size_t ppk, int party, const uint8_t* cwb,
-                     const uint8_t* s0s, const uint8_t* xs, uint8_t* ys);
-
+// ---- Dcf::eval: one function per engine of the plan; first the A/B knobs of eval_stream's instance ladder ----
 #ifndef DCF_SK_PFX
 #define DCF_SK_PFX 1
 #endif
@@ -1471,23 +1502,6 @@ constexpr bool kMkPk2 = DCF_MK_PK2;
 #endif
 constexpr bool kMkNbc4 = DCF_MK_NBC4;  // A/B knob: the N = 4 multi-key top-tree instance (C5 at N = 4)
 
-static int eval_launch(dcf_prg* p, Lease& L, size_t n_bytes, size_t num_keys, size_t ppk, int party,
-                       const uint8_t* cwb, const uint8_t* s0s, const uint8_t* xs, uint8_t* ys) {
-  if (int rc = ensure_ctr(L.w)) return rc;
-  // the block count (dcf_prg_last_eval_blocks) covers the whole call: zeroed once here (the
-  // latency kernels zero it themselves: one command less on a ~100 us call).  The decision and
-  // eval_body's engine choice read the same settings snapshot (L.c).
-  if (!oct_eval(p, L.c, n_bytes, num_keys, (uint64_t)num_keys * ppk))
-    HIP_TRY(hipMemsetAsync(L.w->d_ctr, 0, kCtrBytes, L.st));
-  L.w->last_prefix = 0;
-  L.w->last_prefix_dev = false;
-  phase_mark(p, L, 0);
-  const int rc = eval_body(p, L, n_bytes, num_keys, ppk, party, cwb, s0s, xs, ys);
-  phase_mark(p, L, 2);
-  p->last_ws.store(L.w);
-  return rc;
-}
-
 // Multi-key stream eval: keys per launch.  The kernel's work distribution, point and digest-row
 // indices are 32-bit (kernels_stream.h StreamLane): a launch covers < 2^31 points, and its digest
 // rows key * 8N + level index uint4 pairs (2 * row < 2^31), so at most 2^30 / 8N keys.
@@ -1500,294 +1514,279 @@ size_t dcf_eval_keys_per_launch(size_t n_bytes, size_t points_per_key) {
   return (size_t)mk_keys_per_launch(n_bytes, points_per_key);
 }
 
-static int eval_body(dcf_prg* p, Lease& L, size_t n_bytes, size_t num_keys, size_t ppk, int party, const uint8_t* cwb,
-                     const uint8_t* s0s, const uint8_t* xs, uint8_t* ys) {
-  Workspace* w = L.w;
-  const Cfg& c = L.c;
-  hipStream_t st = L.st;
-  const uint64_t total = (uint64_t)num_keys * ppk;
-  const size_t n = 8 * n_bytes, lam = p->lambda;
-  if (lam > 16) {  // head/tail pipeline: keys with few points batched, else per key
-    phase_mark(p, L, 1);
-    if (wide_batched(p, c, num_keys, ppk))
-      return eval_wide_batch(p, w, n_bytes, num_keys, ppk, party, cwb, s0s, xs, ys, st);
-    for (uint64_t k = 0; k < num_keys; ++k) {
-      int rc = p->kind == 1 ? eval_mmo_wide(p, w, n_bytes, num_keys, k, party, cwb, s0s + k * lam,
-                                            xs + k * ppk * n_bytes, ppk, ys + k * ppk * lam, st)
-                            : eval_wide(p, c, w, n_bytes, num_keys, k, party, cwb, s0s + k * lam,
-                                        xs + k * ppk * n_bytes, ppk, ys + k * ppk * lam, st);
-      if (rc) return rc;
-    }
-    return DCF_OK;
+// One eval call: num_keys keys x ppk points each, key-major, and the parts of its CWB (eval_launch).
+struct EvalArgs {
+  size_t n_bytes, num_keys, ppk;
+  uint64_t total;  // num_keys * ppk
+  int party;
+  const uint8_t *cwb, *s0s, *xs;
+  uint8_t* ys;
+  const uint4 *cws, *cwv, *np1;
+  const uint8_t* cwt;
+};
+
+// LAMBDA >= 32, head/tail pipeline: keys with few points batched, else per key.
+static int eval_wide_engine(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs& a) {
+  const size_t lam = p->lambda;
+  phase_mark(p, L, 1);
+  if (plan.engine == Engine::WideBatch)
+    return eval_wide_batch(p, L.w, a.n_bytes, a.num_keys, a.ppk, a.party, a.cwb, a.s0s, a.xs, a.ys, L.st);
+  for (uint64_t k = 0; k < a.num_keys; ++k) {
+    int rc = p->kind == 1 ? eval_mmo_wide(p, L.w, a.n_bytes, a.num_keys, k, a.party, a.cwb, a.s0s + k * lam,
+                                          a.xs + k * a.ppk * a.n_bytes, a.ppk, a.ys + k * a.ppk * lam, L.st)
+                          : eval_wide(p, plan.depth, L.w, a.n_bytes, a.num_keys, k, a.party, a.cwb, a.s0s + k * lam,
+                                      a.xs + k * a.ppk * a.n_bytes, a.ppk, a.ys + k * a.ppk * lam, L.st);
+    if (rc) return rc;
   }
-  const uint4* cws = (const uint4*)cwb;
-  const uint4* cwv = (const uint4*)(cwb + n * num_keys * lam);
-  const uint8_t* cwt = cwb + 2 * n * num_keys * lam;
-  const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(n_bytes, lam, num_keys));
-  const dim3 grid((unsigned)grid_for(total, p->cus)), block(kBlock);
-  if (p->kind == 1) {  // MMO: lockstep, two blocks per level (the side's s and v), any engine setting
-#define DCF_MMO(MODE)                                                                                          \
-  hipLaunchKernelGGL(k_eval16_mmo<MODE>, grid, block, 0, st, p->d_tab, p->d_rk128, cws, cwv, cwt, np1,            \
-                     (const uint4*)s0s, (uint32_t)party, xs, (uint32_t)n_bytes, (uint64_t)num_keys, (uint64_t)ppk, \
-                     (uint4*)ys, pf)
-    PrefixTable pf{nullptr, 0u};
-    // auto depth: none for small batches (latency-bound: the table's D launches cost what it saves)
-    if (num_keys == 1 && (c.prefix_levels > 0 || total >= (uint64_t)p->cus * kBlock * 2)) {
-      const uint32_t d = prefix_depth(p, c, n_bytes, num_keys, total);
-      if (d) {
-        int rc = try_prefix(p, c, w, n_bytes, party, cws, cwv, cwt, np1, s0s, d, &pf, st);
-        if (rc) return rc;
-        w->last_prefix = pf.levels;
-      }
-    }
-    phase_mark(p, L, 1);
-    if (num_keys == 1) DCF_MMO(0);
-    else if (ppk % 64 == 0) DCF_MMO(1);
-    else DCF_MMO(2);
-#undef DCF_MMO
-    HIP_TRY(hipGetLastError());
-    return DCF_OK;
-  }
-  int mode = c.mode;
-  if (oct_eval(p, c, n_bytes, num_keys, total) && total <= kEvalRow2Max) {
-    // The very smallest batches: one wave per point, two levels per AES chain on right steps
-    // (k_eval16_row2: rows 2 / 3 encrypt the right successor's blocks alongside the level's own).
-    phase_mark(p, L, 1);
-    const uint32_t ppw = per_wg(total, p->cus, kBlock / 64);
-    hipLaunchKernelGGL(k_eval16_row2, dim3((unsigned)((total + ppw - 1) / ppw)), dim3(kBlock), 0, st, p->d_tab,
-                       p->rk[0], cwb, s0s, (uint32_t)party, xs, (uint32_t)n_bytes, ppw, (uint64_t)total, ys, w->d_ctr);
-    HIP_TRY(hipGetLastError());
-    return DCF_OK;
-  }
-  if (oct_eval(p, c, n_bytes, num_keys, total) && total <= kEvalRowMax) {
-    // The smallest batches: 32 lanes per point, one table lookup per lane and AES round
-    // (k_eval16_row: a lone point's level is one 16-lane AES chain).
-    phase_mark(p, L, 1);
-    const uint32_t ppw = per_wg(total, p->cus, kBlock / 32);
-    hipLaunchKernelGGL(k_eval16_row, dim3((unsigned)((total + ppw - 1) / ppw)), dim3(kBlock), 0, st, p->d_tab,
-                       p->rk[0], cwb, s0s, (uint32_t)party, xs, (uint32_t)n_bytes, ppw, (uint64_t)total, ys, w->d_ctr);
-    HIP_TRY(hipGetLastError());
-    return DCF_OK;
-  }
-  if (oct_eval(p, c, n_bytes, num_keys, total)) {
-    // Tiny batches (a single point through the C ABI: benches/dcf.rs bench_eval) are latency-
-    // bound: 8 lanes per point, one AES column each, A and B side by side (k_eval16_oct).
-    phase_mark(p, L, 1);
-    const uint32_t ppw = per_wg(total, p->cus, kBlock / 8);
-    hipLaunchKernelGGL(k_eval16_oct, dim3((unsigned)((total + ppw - 1) / ppw)), dim3(kBlock), 0, st, p->d_tab,
-                       p->rk[0], cwb, s0s, (uint32_t)party, xs, (uint32_t)n_bytes, ppw, (uint64_t)total, ys, w->d_ctr);
-    HIP_TRY(hipGetLastError());
-    return DCF_OK;
-  }
-  // Auto: small batches (fewer points than two per lane of the GPU) are latency-bound: one
-  // point's 8N levels run back to back, so the lockstep walk (A and B of a level in one AES
-  // pass: 8N passes) beats the stream engine (~12N passes); it runs on a lane pair per point
-  // (k_eval16_pair: the even lane encrypts A, the odd lane B), spread over every CU with
-  // workgroups just big enough (C1).  Larger batches: the stream engine, single key or many
-  // (C3 r01: 407 M evals/s vs 332 M lockstep T-table; C5 with the key-major digest).  DCF_EVAL_TTABLE
-  // forces the lockstep walk (k_eval16: A and B every level), which auto takes for many keys at N > 32.
-  if (mode == DCF_EVAL_AUTO && total < (uint64_t)p->cus * kBlock * 2) {
-    PrefixTable spf{nullptr, 0u};
-    if (num_keys == 1) {
-      const uint32_t d = small_prefix_depth(p, c, n_bytes, total);
-      if (d) {
-        int rc = try_prefix(p, c, w, n_bytes, party, cws, cwv, cwt, np1, s0s, d, &spf, st);
-        if (rc) return rc;
-        w->last_prefix = spf.levels;
-      }
-    }
-    phase_mark(p, L, 1);
-    // Whole waves per workgroup.  r06c (C1, same box, 4 alternating runs): rounding the lanes to a
-    // pair instead, so that all 256 CUs get a workgroup (782 lanes, the last wave partial) rather than
-    // 241 (13 whole waves), ran 0.913-0.915 vs 0.894-0.895 ms per step.
-    uint64_t threads = (total * 2 + p->cus - 1) / p->cus;
-    threads = ((threads + 63) / 64) * 64;
-    if (threads > (uint64_t)kBlock) threads = kBlock;
-    const dim3 g2((unsigned)((total * 2 + threads - 1) / threads)), b2((unsigned)threads);
-#define DCF_SMALL(MODE)                                                                                           \
-  hipLaunchKernelGGL(k_eval16_pair<MODE>, g2, b2, 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1,                  \
-                     (const uint4*)s0s, (uint32_t)party, xs, (uint32_t)n_bytes, (uint64_t)num_keys, (uint64_t)ppk,  \
-                     (uint4*)ys, p->d_rk0, MODE == 0 ? spf : PrefixTable{nullptr, 0u})
-    // (r06i: a per-lane block schedule for one key, k_eval16_pair2 — ~100 instead of 128 AES passes
-    // per wave by simulation — ran 31 % slower on C1 and was removed; AB_LOG round 6)
-    if (num_keys == 1) DCF_SMALL(0);
-    else if (ppk % 64 == 0) DCF_SMALL(1);
-    else DCF_SMALL(2);
-#undef DCF_SMALL
-    HIP_TRY(hipGetLastError());
-    return DCF_OK;
-  }
-  if (mode == DCF_EVAL_AUTO) mode = (num_keys == 1 || n_bytes <= 32) ? DCF_EVAL_STREAM : DCF_EVAL_TTABLE;
-  if (mode == DCF_EVAL_STREAM && num_keys > 1 && n_bytes > 32)
-    return fail(DCF_ERR_UNSUPPORTED, "multi-key stream eval: N <= 32");
-  if (mode == DCF_EVAL_STREAM) {
-    constexpr int NS = 2;  // streams per lane
-    const bool xreg = n_bytes % 4 == 0 && n_bytes <= 16, multi = num_keys > 1;
-    if (multi && ppk >= (1ull << 31)) return fail(DCF_ERR_UNSUPPORTED, "multi-key stream eval: 2^31 points per key or more");
-    const uint4* scs = cws;
-    const uint8_t* sct = cwt;
-    PrefixTable pf{nullptr, 0u};
-    if (multi && c.prefix_levels != 0 && n > kMkPfxLevels && ppk >= 32 && num_keys <= (1ull << (31 - kMkPfxLevels))) {
-      // per-key top trees (k_mk_prefix16: 32 rows per key); no room -> walk from the root (same bytes)
-      const size_t need = (size_t)num_keys * (32u << kMkPfxLevels);
-      w->ph.valid = false;  // d_pfx changes hands
-      if (w->pfx_bytes < need) {
-        if (w->d_pfx) {
-          HIP_TRY(hipStreamSynchronize(st));
-          HIP_TRY(hipFree(w->d_pfx));
-          w->d_pfx = nullptr;
-          w->pfx_bytes = 0;
-        }
-        if (hipMalloc(&w->d_pfx, need) != hipSuccess) {
-          (void)hipGetLastError();
-        } else {
-          w->pfx_bytes = need;
-        }
-      }
-      if (w->pfx_bytes >= need) {
-        pf = PrefixTable{(const uint4*)w->d_pfx, kMkPfxLevels};
-        w->last_prefix = kMkPfxLevels;
-      }
-    }
-    if (multi) {
-      // The top trees (k_mk_prefix16: LDS-bound AES, 128 KiB of LDS per workgroup) on the
-      // workspace's second stream while the key-major digest (kernels_stream.h: memory-bound,
-      // 17 KiB per workgroup, so one fits beside a top-tree workgroup on a CU) is written on the
-      // call's stream; the walk waits for both.
-      if (int rc = grow(&w->d_kdig, &w->kdig_bytes, (size_t)num_keys * n * 33, st)) return rc;
-      const bool fork = pf.levels != 0;
-      // Once the top trees are queued on aux, every exit from this block — the normal one and an
-      // error return — joins aux into the call's stream (the walk and the lease's `done` event must
-      // cover them: the next user of this workspace overwrites d_pfx / d_ctr); if the join cannot
-      // be queued, aux is drained on the host instead.
-      struct AuxJoin {
-        Workspace* w;
-        hipStream_t st;
-        bool armed = false;
-        ~AuxJoin() {
-          if (!armed) return;
-          if (hipEventRecord(w->aux_ev[1], w->aux) != hipSuccess || hipStreamWaitEvent(st, w->aux_ev[1], 0) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(w->aux);
-          }
-        }
-      } join{w, st};
-      if (fork) {
-        if (!w->aux) HIP_TRY(hipStreamCreateWithFlags(&w->aux, hipStreamNonBlocking));
-        for (auto& e : w->aux_ev)
-          if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(w->aux_ev[0], st));
-        HIP_TRY(hipStreamWaitEvent(w->aux, w->aux_ev[0], 0));
-        join.armed = true;
-        hipLaunchKernelGGL(k_mk_prefix16<true>,
-                           dim3((unsigned)(((num_keys << kMkPfxRoot) + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                           w->aux, p->d_tab, p->rk[0], cws, cwv, cwt, (const uint4*)s0s, (uint32_t)party,
-                           (uint64_t)num_keys, (uint4*)w->d_pfx, p->d_rk0, w->d_ctr);
-        HIP_TRY(hipGetLastError());
-      }
-      hipLaunchKernelGGL(k_cw_keymajor, dim3((unsigned)((num_keys + kKmKeys - 1) / kKmKeys), (unsigned)((n + kKmLevs - 1) / kKmLevs)),
-                         dim3(kKmThreads), 0, st, cws, cwv, cwt, (uint32_t)n, (uint64_t)num_keys, (uint4*)w->d_kdig,
-                         w->d_kdig + (size_t)num_keys * n * 32);
-      HIP_TRY(hipGetLastError());
-      // (the join runs here, as `join` leaves scope: the walk below waits for the top trees)
-      scs = (const uint4*)w->d_kdig;
-      sct = w->d_kdig + (size_t)num_keys * n * 32;
-    }
-    const uint32_t* pst = nullptr;  // cross-call table: the walk reads its depth here
-    if (!multi) {
-      const uint32_t d = prefix_depth(p, c, n_bytes, num_keys, total);
-      // the cross-call table: dcf_eval_device calls that run a single-key table-start instance
-      if (d && L.reuse && kSkPfx && (n_bytes == 16 || n_bytes == 4) && total < (1ull << 31)) {
-        int rc = reuse_prefix(p, c, w, n_bytes, party, cwb, cws, cwv, cwt, np1, s0s, d, total, &pf, st);
-        if (rc) return rc;
-        w->last_prefix = pf.levels;
-        if (pf.levels) {
-          pst = w->d_pst;
-          w->last_prefix_dev = true;
-        }
-      } else if (d) {
-        int rc = try_prefix(p, c, w, n_bytes, party, cws, cwv, cwt, np1, s0s, d, &pf, st);
-        if (rc) return rc;
-        w->last_prefix = pf.levels;
-      }
-    }
-    phase_mark(p, L, 1);
-    // One launch covers < 2^31 points (multi-key: mk_keys_per_launch whole keys).  Larger
-    // batches run as several launches over consecutive points / whole keys, sharing the table
-    // and digest built above.
-    const uint64_t kpl = multi ? mk_keys_per_launch(n_bytes, ppk) : 1;
-    const uint64_t ppl = multi ? kpl * ppk : (1ull << 31);  // points per launch
-    for (uint64_t c0 = 0; c0 < total; c0 += ppl) {
-      const uint64_t cnt = std::min<uint64_t>(ppl, total - c0), k0 = multi ? c0 / ppk : 0, kc = multi ? cnt / ppk : 1;
-      // each walk's work counter starts at 0 (the block count beside it keeps the per-key top
-      // trees' blocks): eval_launch zeroed it for the first launch (the table builds and the
-      // digest do not touch it), so a one-launch eval has no fill between the build and the walk
-      if (c0 > 0) HIP_TRY(hipMemsetAsync(w->d_ctr, 0, 8, st));
-      const uint64_t units = (cnt + kStreamUnit - 1) / kStreamUnit;
-      uint64_t blocks = (units + 15) / 16;
-      if (blocks > (uint64_t)p->cus) blocks = (uint64_t)p->cus;
-      const uint4* lcs = multi ? scs + k0 * 2 * n : scs;
-      const uint8_t* lct = multi ? sct + k0 * n : sct;
-      const uint4* lnp1 = np1 + k0;
-      const uint8_t* lxs = xs + c0 * n_bytes;
-      uint8_t* lys = ys + c0 * lam;
-      const uint8_t* ls0 = s0s + k0 * lam;
-      const PrefixTable lpf = (multi && pf.levels) ? PrefixTable{pf.sv + 2 * (k0 << pf.levels), pf.levels} : pf;
-#define DCF_STREAM(XR, MK, PF, NBC) DCF_STREAM7(XR, MK, PF, NBC, false, false)
-#define DCF_STREAM6(XR, MK, PF, NBC, PK2) DCF_STREAM7(XR, MK, PF, NBC, PK2, false)
-#define DCF_STREAM7(XR, MK, PF, NBC, PK2, STG)                                                                  \
-  hipLaunchKernelGGL((k_eval16_stream<NS, XR, MK, PF, NBC, PK2, STG>), dim3((unsigned)blocks), block, 0, st, p->d_tab, \
-                     p->rk[0],                                                                                 \
-                     lcs, cwv, lct, lnp1, (const uint4*)ls0, (uint32_t)party, lxs, (uint32_t)n_bytes, (uint64_t)kc, \
-                     (uint64_t)ppk, (uint64_t)cnt, w->d_ctr, (uint4*)lys, lpf, p->d_rk0, pst)
-      // multi-key: an instance for "per-key top trees present" (no root-seed start path: 48 -> 33
-      // SGPR spills; C5 r03c A/B 414.6 / 413.7 vs 408.5 / 408.1 M evals/s), and of it one with the
-      // x width fixed at N = 16 (C5: 33 -> 18 SGPR spills, 121 -> 119 VGPRs, r05k).  Single key, x in
-      // registers: N = 16 (C1 / C3) and N = 4 (C2) with the x width fixed at compile time (a
-      // point's start loads x without width branches: C2 starts a point every ~13 AES slots).
-      if (multi && lpf.levels) {
-        if (xreg && n_bytes == 16 && kMkNbc16 && kMkPk2 && (ppk & (ppk - 1)) == 0) DCF_STREAM6(true, true, true, 16, true);
-        else if (xreg && n_bytes == 16 && kMkNbc16) DCF_STREAM(true, true, true, 16);
-        else if (xreg && n_bytes == 4 && kMkNbc4 && (ppk & (ppk - 1)) == 0) DCF_STREAM6(true, true, true, 4, true);
-        else if (xreg) DCF_STREAM(true, true, true, 0);
-        else DCF_STREAM(false, true, true, 0);
-      } else if (multi) {
-        if (xreg) DCF_STREAM(true, true, false, 0);
-        else DCF_STREAM(false, true, false, 0);
-      } else if (xreg && n_bytes == 16 && lpf.levels && kSkPfx) {
-        DCF_STREAM(true, false, true, 16);  // every start below the shared prefix: no fresh-x-word path
-      } else if (xreg && n_bytes == 16) {
-        DCF_STREAM(true, false, false, 16);
-      } else if (xreg && n_bytes == 4 && lpf.levels && kSkPfx && kStg) {
-        DCF_STREAM7(true, false, true, 4, false, true);  // rows staged two iterations ahead (C2)
-      } else if (xreg && n_bytes == 4 && lpf.levels && kSkPfx) {
-        DCF_STREAM(true, false, true, 4);
-      } else if (xreg && n_bytes == 4) {
-        DCF_STREAM(true, false, false, 4);
-      } else if (xreg) {
-        DCF_STREAM(true, false, false, 0);
-      } else {
-        DCF_STREAM(false, false, false, 0);
-      }
-#undef DCF_STREAM
-#undef DCF_STREAM6
-#undef DCF_STREAM7
-      HIP_TRY(hipGetLastError());
-    }
-  } else {  // lockstep T-table, 64-point units from the work counter
-    if ((total + 63) / 64 > 0xFFFFFFFFull) return fail(DCF_ERR_UNSUPPORTED, "more than 2^32 64-point units");
-    phase_mark(p, L, 1);
-#define DCF_TT(MODE)                                                                                         \
-  hipLaunchKernelGGL(k_eval16<MODE>, grid, block, 0, st, p->d_tab, p->rk[0], cws, cwv, cwt, np1,               \
-                     (const uint4*)s0s, (uint32_t)party, xs, (uint32_t)n_bytes, (uint64_t)num_keys, (uint64_t)ppk, \
-                     (uint4*)ys, w->d_ctr)
-    if (num_keys == 1) DCF_TT(0);
-    else if (ppk % 64 == 0) DCF_TT(1);
-    else DCF_TT(2);
-#undef DCF_TT
-  }
+  return DCF_OK;
+}
+
+// MMO at LAMBDA = 16: lockstep, two blocks per level (the side's s and v), any engine setting.
+static int eval_mmo16(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs& a) {
+  static constexpr decltype(&k_eval16_mmo<0>) kKernel[3] = {k_eval16_mmo<0>, k_eval16_mmo<1>, k_eval16_mmo<2>};
+  PrefixTable pf{nullptr, 0u};
+  if (int rc = try_prefix(p, L.c, L.w, a.n_bytes, a.party, a.cws, a.cwv, a.cwt, a.np1, a.s0s, plan.depth, &pf, L.st))
+    return rc;
+  phase_mark(p, L, 1);
+  hipLaunchKernelGGL(kKernel[plan.key_mode], dim3((unsigned)grid_for(a.total, p->cus)), dim3(kBlock), 0, L.st,
+                     p->d_tab, p->d_rk128, a.cws, a.cwv, a.cwt, a.np1, (const uint4*)a.s0s, (uint32_t)a.party, a.xs,
+                     (uint32_t)a.n_bytes, (uint64_t)a.num_keys, (uint64_t)a.ppk, (uint4*)a.ys, pf);
   HIP_TRY(hipGetLastError());
   return DCF_OK;
+}
+
+// The latency kernels (kernels_lat.h; each zeroes d_ctr itself), {kernel, lanes per point}.  row2, the very
+// smallest batches: one wave per point, two levels per AES chain on right steps (rows 2 / 3 encrypt the right
+// successor's blocks alongside the level's own).  row, the smallest: one table lookup per lane and AES round (a
+// lone point's level is one 16-lane AES chain).  oct: tiny batches (a single point through the C ABI:
+// benches/dcf.rs bench_eval) are latency-bound: one AES column per lane, A and B side by side.
+static int eval_latency(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs& a) {
+  static constexpr std::pair<decltype(&k_eval16_oct), uint32_t> kLat[3] = {
+      {k_eval16_row2, 64}, {k_eval16_row, 32}, {k_eval16_oct, 8}};
+  const auto& lat = kLat[plan.engine == Engine::Row2 ? 0 : plan.engine == Engine::Row ? 1 : 2];
+  phase_mark(p, L, 1);
+  const uint32_t ppw = per_wg(a.total, p->cus, kBlock / lat.second);
+  hipLaunchKernelGGL(lat.first, dim3((unsigned)((a.total + ppw - 1) / ppw)), dim3(kBlock), 0, L.st, p->d_tab, p->rk[0],
+                     a.cwb, a.s0s, (uint32_t)a.party, a.xs, (uint32_t)a.n_bytes, ppw, a.total, a.ys, L.w->d_ctr);
+  HIP_TRY(hipGetLastError());
+  return DCF_OK;
+}
+
+// The pair walk (why and when: plan_eval); one key walks below its own table (small_prefix_depth).
+static int eval_pair(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs& a) {
+  static constexpr decltype(&k_eval16_pair<0>) kKernel[3] = {k_eval16_pair<0>, k_eval16_pair<1>, k_eval16_pair<2>};
+  const uint64_t total = a.total;
+  PrefixTable spf{nullptr, 0u};
+  if (int rc = try_prefix(p, L.c, L.w, a.n_bytes, a.party, a.cws, a.cwv, a.cwt, a.np1, a.s0s, plan.depth, &spf, L.st))
+    return rc;
+  phase_mark(p, L, 1);
+  // Whole waves per workgroup.  r06c (C1, same box, 4 alternating runs): rounding the lanes to a
+  // pair instead, so that all 256 CUs get a workgroup (782 lanes, the last wave partial) rather than
+  // 241 (13 whole waves), ran 0.913-0.915 vs 0.894-0.895 ms per step.
+  uint64_t threads = (total * 2 + p->cus - 1) / p->cus;
+  threads = std::min<uint64_t>(((threads + 63) / 64) * 64, kBlock);
+  const dim3 g2((unsigned)((total * 2 + threads - 1) / threads)), b2((unsigned)threads);
+  // (r06i: a per-lane block schedule for one key, k_eval16_pair2 — ~100 instead of 128 AES passes
+  // per wave by simulation — ran 31 % slower on C1 and was removed; AB_LOG round 6)  Table: mode 0 only.
+  hipLaunchKernelGGL(kKernel[plan.key_mode], g2, b2, 0, L.st, p->d_tab, p->rk[0], a.cws, a.cwv, a.cwt, a.np1,
+                     (const uint4*)a.s0s, (uint32_t)a.party, a.xs, (uint32_t)a.n_bytes, (uint64_t)a.num_keys,
+                     (uint64_t)a.ppk, (uint4*)a.ys, p->d_rk0, plan.key_mode == 0 ? spf : PrefixTable{nullptr, 0u});
+  HIP_TRY(hipGetLastError());
+  return DCF_OK;
+}
+
+// Stream engine, several keys: the per-key top trees (*pf; none: the walk starts at the root) and
+// the key-major CW digest in w->d_kdig.
+static int stream_multikey_prep(dcf_prg* p, Lease& L, const EvalArgs& a, PrefixTable* pf) {
+  Workspace* w = L.w;
+  hipStream_t st = L.st;
+  const size_t n = 8 * a.n_bytes, num_keys = a.num_keys;
+  if (L.c.prefix_levels != 0 && n > kMkPfxLevels && a.ppk >= 32 && num_keys <= (1ull << (31 - kMkPfxLevels))) {
+    // per-key top trees (k_mk_prefix16: 32 rows per key); no room -> walk from the root (same bytes)
+    const size_t need = (size_t)num_keys * (32u << kMkPfxLevels);
+    w->ph.valid = false;  // d_pfx changes hands
+    hipError_t oom;
+    if (int rc = reserve_pfx(w, need, st, &oom)) return rc;
+    if (w->pfx_bytes >= need) {
+      *pf = PrefixTable{(const uint4*)w->d_pfx, kMkPfxLevels};
+      w->last_prefix = kMkPfxLevels;
+    }
+  }
+  // The top trees (k_mk_prefix16: LDS-bound AES, 128 KiB of LDS per workgroup) on the
+  // workspace's second stream while the key-major digest (kernels_stream.h: memory-bound,
+  // 17 KiB per workgroup, so one fits beside a top-tree workgroup on a CU) is written on the
+  // call's stream; the walk waits for both.
+  if (int rc = grow(&w->d_kdig, &w->kdig_bytes, (size_t)num_keys * n * 33, st)) return rc;
+  const bool fork = pf->levels != 0;
+  // Once the top trees are queued on aux, every exit from this function — the normal one and an
+  // error return — joins aux into the call's stream (the walk and the lease's `done` event must
+  // cover them: the next user of this workspace overwrites d_pfx / d_ctr); if the join cannot
+  // be queued, aux is drained on the host instead.
+  struct AuxJoin {
+    Workspace* w;
+    hipStream_t st;
+    bool armed = false;
+    ~AuxJoin() {
+      if (!armed) return;
+      if (hipEventRecord(w->aux_ev[1], w->aux) != hipSuccess || hipStreamWaitEvent(st, w->aux_ev[1], 0) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(w->aux);
+      }
+    }
+  } join{w, st};
+  if (fork) {
+    if (!w->aux) HIP_TRY(hipStreamCreateWithFlags(&w->aux, hipStreamNonBlocking));
+    for (auto& e : w->aux_ev)
+      if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(w->aux_ev[0], st));
+    HIP_TRY(hipStreamWaitEvent(w->aux, w->aux_ev[0], 0));
+    join.armed = true;
+    hipLaunchKernelGGL(k_mk_prefix16<true>, dim3((unsigned)(((num_keys << kMkPfxRoot) + kBlock - 1) / kBlock)),
+                       dim3(kBlock), 0, w->aux, p->d_tab, p->rk[0], a.cws, a.cwv, a.cwt, (const uint4*)a.s0s,
+                       (uint32_t)a.party, (uint64_t)num_keys, (uint4*)w->d_pfx, p->d_rk0, w->d_ctr);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_cw_keymajor, dim3((unsigned)((num_keys + kKmKeys - 1) / kKmKeys), (unsigned)((n + kKmLevs - 1) / kKmLevs)),
+                     dim3(kKmThreads), 0, st, a.cws, a.cwv, a.cwt, (uint32_t)n, (uint64_t)num_keys, (uint4*)w->d_kdig,
+                     w->d_kdig + (size_t)num_keys * n * 32);
+  HIP_TRY(hipGetLastError());
+  return DCF_OK;  // (the join runs here, as `join` leaves scope: the walk waits for the top trees)
+}
+
+// Stream engine, one key: the shared-prefix table of the plan's depth.  The cross-call table
+// (reuse_prefix; last_prefix_dev: the walk reads its depth from d_pst): dcf_eval_device calls that
+// run a single-key table-start instance.
+static int stream_table(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs& a, PrefixTable* pf) {
+  if (!(plan.depth && L.reuse && kSkPfx && (a.n_bytes == 16 || a.n_bytes == 4) && a.total < (1ull << 31)))
+    return try_prefix(p, L.c, L.w, a.n_bytes, a.party, a.cws, a.cwv, a.cwt, a.np1, a.s0s, plan.depth, pf, L.st);
+  if (int rc = reuse_prefix(p, L.c, L.w, a.n_bytes, a.party, a.cwb, a.cws, a.cwv, a.cwt, a.np1, a.s0s, plan.depth,
+                            a.total, pf, L.st))
+    return rc;
+  L.w->last_prefix = pf->levels;
+  L.w->last_prefix_dev = pf->levels != 0;
+  return DCF_OK;
+}
+
+// Stream engine: table preparation (several keys: top trees and digest; one key: the table), then the
+// walk.  One launch covers < 2^31 points (multi-key: mk_keys_per_launch whole keys).  Larger batches run
+// as several launches over consecutive points / whole keys, sharing the table and the digest.
+static int eval_stream(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs& a) {
+  constexpr int NS = 2;  // streams per lane
+  Workspace* w = L.w;
+  hipStream_t st = L.st;
+  PrefixTable pf{nullptr, 0u};
+  if (int rc = a.num_keys > 1 ? stream_multikey_prep(p, L, a, &pf) : stream_table(p, L, plan, a, &pf)) return rc;
+  phase_mark(p, L, 1);
+  const size_t n_bytes = a.n_bytes, n = 8 * n_bytes, ppk = a.ppk;
+  const uint64_t total = a.total;
+  const uint32_t* pst = w->last_prefix_dev ? w->d_pst : nullptr;  // cross-call table: its depth
+  const bool xreg = n_bytes % 4 == 0 && n_bytes <= 16, multi = a.num_keys > 1;
+  // several keys: the key-major digest of stream_multikey_prep
+  const uint4* scs = multi ? (const uint4*)w->d_kdig : a.cws;
+  const uint8_t* sct = multi ? w->d_kdig + (size_t)a.num_keys * n * 32 : a.cwt;
+  const uint64_t kpl = multi ? mk_keys_per_launch(n_bytes, ppk) : 1;
+  const uint64_t ppl = multi ? kpl * ppk : (1ull << 31);  // points per launch
+  for (uint64_t c0 = 0; c0 < total; c0 += ppl) {
+    const uint64_t cnt = std::min<uint64_t>(ppl, total - c0), k0 = multi ? c0 / ppk : 0, kc = multi ? cnt / ppk : 1;
+    // each walk's work counter starts at 0 (the block count beside it keeps the per-key top
+    // trees' blocks): eval_launch zeroed it for the first launch (the table builds and the
+    // digest do not touch it), so a one-launch eval has no fill between the build and the walk
+    if (c0 > 0) HIP_TRY(hipMemsetAsync(w->d_ctr, 0, 8, st));
+    const uint64_t units = (cnt + kStreamUnit - 1) / kStreamUnit;
+    const uint64_t blocks = std::min<uint64_t>((units + 15) / 16, (uint64_t)p->cus);
+    const uint4* lcs = multi ? scs + k0 * 2 * n : scs;
+    const uint8_t* lct = multi ? sct + k0 * n : sct;
+    const uint4* lnp1 = a.np1 + k0;
+    const uint8_t* lxs = a.xs + c0 * n_bytes;
+    uint8_t* lys = a.ys + c0 * 16;
+    const uint8_t* ls0 = a.s0s + k0 * 16;
+    const PrefixTable lpf = (multi && pf.levels) ? PrefixTable{pf.sv + 2 * (k0 << pf.levels), pf.levels} : pf;
+#define DCF_STREAM(XR, MK, PF, NBC, PK2, STG)                                                                        \
+  hipLaunchKernelGGL((k_eval16_stream<NS, XR, MK, PF, NBC, PK2, STG>), dim3((unsigned)blocks), dim3(kBlock), 0, st,   \
+                     p->d_tab, p->rk[0], lcs, a.cwv, lct, lnp1, (const uint4*)ls0, (uint32_t)a.party, lxs,          \
+                     (uint32_t)n_bytes, (uint64_t)kc, (uint64_t)ppk, (uint64_t)cnt, w->d_ctr, (uint4*)lys, lpf,       \
+                     p->d_rk0, pst)
+    // multi-key: an instance for "per-key top trees present" (no root-seed start path: 48 -> 33
+    // SGPR spills; C5 r03c A/B 414.6 / 413.7 vs 408.5 / 408.1 M evals/s), and of it one with the
+    // x width fixed at N = 16 (C5: 33 -> 18 SGPR spills, 121 -> 119 VGPRs, r05k).  Single key, x in
+    // registers: N = 16 (C1 / C3) and N = 4 (C2) with the x width fixed at compile time (a
+    // point's start loads x without width branches: C2 starts a point every ~13 AES slots).
+    if (multi && lpf.levels) {
+      if (xreg && n_bytes == 16 && kMkNbc16 && kMkPk2 && (ppk & (ppk - 1)) == 0) DCF_STREAM(true, true, true, 16, true, false);
+      else if (xreg && n_bytes == 16 && kMkNbc16) DCF_STREAM(true, true, true, 16, false, false);
+      else if (xreg && n_bytes == 4 && kMkNbc4 && (ppk & (ppk - 1)) == 0) DCF_STREAM(true, true, true, 4, true, false);
+      else if (xreg) DCF_STREAM(true, true, true, 0, false, false);
+      else DCF_STREAM(false, true, true, 0, false, false);
+    } else if (multi) {
+      if (xreg) DCF_STREAM(true, true, false, 0, false, false);
+      else DCF_STREAM(false, true, false, 0, false, false);
+    } else if (xreg && n_bytes == 16 && lpf.levels && kSkPfx) {
+      DCF_STREAM(true, false, true, 16, false, false);  // every start below the shared prefix: no fresh-x-word path
+    } else if (xreg && n_bytes == 16) {
+      DCF_STREAM(true, false, false, 16, false, false);
+    } else if (xreg && n_bytes == 4 && lpf.levels && kSkPfx && kStg) {
+      DCF_STREAM(true, false, true, 4, false, true);  // rows staged two iterations ahead (C2)
+    } else if (xreg && n_bytes == 4 && lpf.levels && kSkPfx) {
+      DCF_STREAM(true, false, true, 4, false, false);
+    } else if (xreg && n_bytes == 4) {
+      DCF_STREAM(true, false, false, 4, false, false);
+    } else if (xreg) {
+      DCF_STREAM(true, false, false, 0, false, false);
+    } else {
+      DCF_STREAM(false, false, false, 0, false, false);
+    }
+#undef DCF_STREAM
+    HIP_TRY(hipGetLastError());
+  }
+  return DCF_OK;
+}
+
+// Lockstep T-table walk (k_eval16), 64-point units from the work counter.
+static int eval_ttable(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs& a) {
+  static constexpr decltype(&k_eval16<0>) kKernel[3] = {k_eval16<0>, k_eval16<1>, k_eval16<2>};
+  phase_mark(p, L, 1);
+  hipLaunchKernelGGL(kKernel[plan.key_mode], dim3((unsigned)grid_for(a.total, p->cus)), dim3(kBlock), 0, L.st,
+                     p->d_tab, p->rk[0], a.cws, a.cwv, a.cwt, a.np1, (const uint4*)a.s0s, (uint32_t)a.party, a.xs,
+                     (uint32_t)a.n_bytes, (uint64_t)a.num_keys, (uint64_t)a.ppk, (uint4*)a.ys, L.w->d_ctr);
+  HIP_TRY(hipGetLastError());
+  return DCF_OK;
+}
+
+// Dcf::eval of the call `a` by the engine of its plan.  Phase mark 1 (dcf_prg_set_phase_timing) sits in
+// every engine before the walk kernel, after any table / digest preparation.
+static int eval_body(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs& a) {
+  if (plan.unsupported) return fail(DCF_ERR_UNSUPPORTED, plan.unsupported);
+  switch (plan.engine) {
+    case Engine::WideBatch:
+    case Engine::WidePerKey: return eval_wide_engine(p, L, plan, a);
+    case Engine::Mmo16: return eval_mmo16(p, L, plan, a);
+    case Engine::Pair: return eval_pair(p, L, plan, a);
+    case Engine::Stream: return eval_stream(p, L, plan, a);
+    case Engine::TTable: return eval_ttable(p, L, plan, a);
+    default: return eval_latency(p, L, plan, a);  // Row2, Row, Oct
+  }
+}
+
+// Dcf::eval of K keys x ppk points on the lease's stream (arguments checked by the caller; the
+// range and multi-GPU drivers come through here as well).  Phase marks: 0 at entry, 2 at the end.
+static int eval_launch(dcf_prg* p, Lease& L, size_t n_bytes, size_t num_keys, size_t ppk, int party,
+                       const uint8_t* cwb, const uint8_t* s0s, const uint8_t* xs, uint8_t* ys) {
+  if (int rc = ensure_ctr(L.w)) return rc;
+  const EvalPlan plan = plan_eval(p, L.c, n_bytes, num_keys, ppk);
+  // the block count (dcf_prg_last_eval_blocks) covers the whole call: zeroed once here (the
+  // latency kernels zero it themselves: one command less on a ~100 us call)
+  if (!plan.latency()) HIP_TRY(hipMemsetAsync(L.w->d_ctr, 0, kCtrBytes, L.st));
+  L.w->last_prefix = 0;
+  L.w->last_prefix_dev = false;
+  phase_mark(p, L, 0);
+  const size_t n = 8 * n_bytes, lam = p->lambda;
+  const EvalArgs a{n_bytes, num_keys, ppk, (uint64_t)num_keys * ppk, party, cwb, s0s, xs, ys, (const uint4*)cwb,
+                   (const uint4*)(cwb + n * num_keys * lam),
+                   (const uint4*)(cwb + dcf_cwb_np1_offset(n_bytes, lam, num_keys)), cwb + 2 * n * num_keys * lam};
+  const int rc = eval_body(p, L, plan, a);
+  phase_mark(p, L, 2);
+  p->last_ws.store(L.w);
+  return rc;
 }
 
 static int check_eval_args(dcf_prg* p, size_t n_bytes, int party, uint64_t total, const void* cwb, const void* s0s,
@@ -1929,7 +1928,8 @@ static int host_eval(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* 
   Workspace* w = L.w;
   const size_t lam = p->lambda;
   const size_t ko = 0, so0 = align256(cwb_len), xo = so0 + 256, yo = xo + align256(m * nb);
-  if (oct_eval(p, L.c, nb, 1, m) && yo + m * lam <= kTinyBytes) {
+  const EvalPlan plan = plan_eval(p, L.c, nb, 1, m);  // of the whole batch: which host path
+  if (plan.latency() && yo + m * lam <= kTinyBytes) {
     uint8_t* d = nullptr;
     if (int rc = ensure_tiny(w, &d)) return rc;
     uint8_t* h = w->h_tiny;
@@ -1946,8 +1946,7 @@ static int host_eval(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* 
   // launch, one stream sync and one host copy out — no staging DMAs or chunk events (a C1-size
   // call is one chunk, its copies cannot overlap its kernel anyway).  The key goes to device
   // memory first: the walk reads a correction word per level.
-  if (lam == 16 && L.c.mode == DCF_EVAL_AUTO && m < (uint64_t)p->cus * kBlock * 2 &&
-      m * (nb + lam) <= kHostMidBytes) {
+  if (plan.small && m * (nb + lam) <= kHostMidBytes) {
     const size_t kb = align256(cwb_len) + align256(lam);
     const size_t mx = align256(m * nb), need = kb + mx + m * lam;
     uint8_t* d = nullptr;

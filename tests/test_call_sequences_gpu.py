@@ -281,7 +281,7 @@ class Settings:
 
 
 def engine(config, st, step):
-    """The kernel family an eval step runs (dcf_hip.hip eval_body), None for other steps."""
+    """The kernel family an eval step runs (dcf_hip.hip plan_eval), None for other steps."""
     kind, lam, _ = CONFIGS[config]
     if step.kind not in ("host_eval", "eval_device", "eval_multikey"):
         return None

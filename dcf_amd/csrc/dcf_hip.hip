@@ -2448,75 +2448,86 @@ uint64_t dcf_eval_range_wide_points_per_launch(size_t n_bytes, size_t lambda) {
   return n_bytes && n_bytes <= 16 && lambda >= 32 ? range_wide_points(n_bytes) : 0;
 }
 
-// The one workspace allocation of a launch group of n outputs: [t-vectors, 64 B per output
-// (lambda > 32; + 256 B as eval_wide: a tail's clamped t loads run past the last row) | two
-// ping-pong buffers of the 80-byte nodes of the level above the register tail | the roots'
+// The one workspace allocation of a launch group of `keys` keys of n outputs each: [t-vectors, 64 B
+// per output (lambda > 32; + 256 B as eval_wide: a tail's clamped t loads run past the last row) |
+// two ping-pong buffers of the 80-byte nodes of the level above the register tail | the roots'
 // t-vector prefixes, 64 B each (lambda > 32) | kRangeCtrs work counters].  The paired-slot tail's
 // per-workgroup counters are a buffer of their own (Workspace::d_tctr), not part of this.
 struct RangeWideWs {
   size_t tv, buf, pre, total;
 };
-static RangeWideWs range_wide_ws(uint64_t n, uint32_t h, size_t lam) {
+static RangeWideWs range_wide_ws(uint64_t n, uint32_t h, size_t lam, uint64_t keys = 1,
+                                 uint32_t tail = kRangeWideTail) {
   RangeWideWs r;
-  const uint64_t maxroots = (n >> h) + 2;
+  const uint64_t maxroots = keys * ((n >> h) + 2);
+  n *= keys;
   r.tv = lam > 32 ? align256(n * kTWords * 4) + 256 : 0;
-  r.buf = h ? align256((maxroots * 80) << (h - kRangeWideTail)) : 0;
+  r.buf = h ? align256((maxroots * 80) << (h - tail)) : 0;
   r.pre = h && lam > 32 ? align256(maxroots * kTWords * 4) : 0;
   r.total = r.tv + 2 * r.buf + r.pre + kRangeCtrs * sizeof(uint32_t);
   return r;
 }
 
-// One launch group: the n points from xa into ys.  MASK: lambda = 32, the kernels' form without
-// t-vectors.  The caller has sized the workspace (range_wide_ws), built the CW digest and zeroed the
-// block count.
-extern "C++" template <bool MASK>
-static int range_wide_group(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
-                            const RangeX xa, uint64_t n, uint32_t h, const RangeWideWs& ws, uint8_t* ys) {
+// One launch group: keys [key0, key0 + keys) of a K-key block over the n points from xa; the outputs
+// of key key0 + k go to rows [k * n, (k + 1) * n) of ys (several keys in a group: n is the call's
+// count).  MASK: lambda = 32, the kernels' form without t-vectors.  KP: the kernels' key policy —
+// RangeOneKey takes keys = 1 (any key0 of any K: the key is read in place).  The caller has sized
+// the workspace (range_wide_ws), built the CW digest of the group's keys (dig_t behind its
+// keys * 8N * 64 bytes) and zeroed the block count.
+extern "C++" template <bool MASK, class KP>
+static int range_wide_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb,
+                            const uint8_t* s0s, uint64_t key0, uint64_t keys, const RangeX xa, uint64_t n, uint32_t h,
+                            const RangeWideWs& ws, uint8_t* ys) {
   hipStream_t st = L.st;
   Workspace* w = L.w;
   const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * nb);
-  const uint8_t* cwv = cwb + (size_t)nlev * lam;
-  const uint8_t* np1 = cwb + dcf_cwb_np1_offset(nb, lam, 1);
+  const uint8_t* cwv = cwb + (size_t)nlev * K * lam;
+  const uint8_t* np1 = cwb + dcf_cwb_np1_offset(nb, lam, K);
+  const uint4* np1k = (const uint4*)(np1 + key0 * lam);  // the group's first key
+  const uint8_t* s0 = s0s + key0 * lam;
   const uint4* dig = (const uint4*)w->d_dig;
-  const uint8_t* dig_t = w->d_dig + (size_t)nlev * 64;
+  const uint8_t* dig_t = w->d_dig + (size_t)keys * nlev * 64;
   unsigned long long* blocks = reinterpret_cast<unsigned long long*>(w->d_ctr) + 1;
   uint32_t* tvec = MASK ? nullptr : reinterpret_cast<uint32_t*>(w->d_ws);
   const auto roots_grid = [&](uint64_t roots) { return dim3((unsigned)std::min<uint64_t>((uint64_t)p->cus, (roots + 63) / 64)); };
   if (h == 0) {  // every point is its own root: the root walk writes y[0:32) and the t-vector
-    hipLaunchKernelGGL((k_range_roots_wide<true, MASK>), roots_grid(n), dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig, dig_t,
-                       (const uint4*)np1, (const uint4*)s0, (uint32_t)party, xa, nlev, (uint32_t)n, (uint4*)nullptr, tvec,
-                       ys, lam, blocks);
+    const uint64_t total = keys * n;
+    hipLaunchKernelGGL((k_range_roots_wide<true, MASK, KP>), roots_grid(total), dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig,
+                       dig_t, np1k, (const uint4*)s0, KP::make(nlev, (uint32_t)n), (uint32_t)party, xa, nlev, (uint32_t)total,
+                       (uint4*)nullptr, tvec, ys, lam, blocks);
     HIP_TRY(hipGetLastError());
   } else {
-    const RangeGeom g = range_geom(xa, n, h, kRangeWideTail);
+    constexpr uint32_t tail = KP::kPerLane ? kRangeWideTailKeys : kRangeWideTail;  // register depth of the tail
+    const RangeGeom g = range_geom(xa, n, h, tail);
     const uint32_t w0 = (nlev - h + 1) >> 4;  // the t-vector word of the first row below the roots
     uint4* cur = (uint4*)(w->d_ws + ws.tv);
     uint4* nxt = (uint4*)(w->d_ws + ws.tv + ws.buf);
     uint32_t* tpre = MASK ? nullptr : (uint32_t*)(w->d_ws + ws.tv + 2 * ws.buf);
     uint32_t* ctrs = (uint32_t*)(w->d_ws + ws.tv + 2 * ws.buf + ws.pre);
     HIP_TRY(hipMemsetAsync(ctrs, 0, kRangeCtrs * sizeof(uint32_t), st));
-    hipLaunchKernelGGL((k_range_roots_wide<false, MASK>), roots_grid(g.nroots), dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig,
-                       dig_t, (const uint4*)np1, (const uint4*)s0, (uint32_t)party, g.pfx, nlev - h, (uint32_t)g.nroots, cur,
-                       tpre, (uint8_t*)nullptr, lam, blocks);
+    const uint64_t total = keys * g.nroots;
+    hipLaunchKernelGGL((k_range_roots_wide<false, MASK, KP>), roots_grid(total), dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig,
+                       dig_t, np1k, (const uint4*)s0, KP::make(nlev, (uint32_t)g.nroots), (uint32_t)party, g.pfx, nlev - h,
+                       (uint32_t)total, cur, tpre, (uint8_t*)nullptr, lam, blocks);
     HIP_TRY(hipGetLastError());
-    for (uint32_t k = 0; k < g.m; ++k) {  // level 8N - h + k: nroots << k parents
-      const uint64_t parents = g.nroots << k;
-      hipLaunchKernelGGL((k_range_level_wide<MASK>), dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st,
-                         p->d_tab, p->d_rk2, dig, dig_t, nlev - h + k, w0, (uint32_t)parents, (const uint4*)cur, nxt, ctrs + k,
-                         blocks);
+    for (uint32_t k = 0; k < g.m; ++k) {  // level 8N - h + k: nroots << k parents per key
+      const uint64_t parents = total << k;
+      hipLaunchKernelGGL((k_range_level_wide<MASK, KP>), dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st,
+                         p->d_tab, p->d_rk2, dig, dig_t, KP::make(nlev, (uint32_t)(g.nroots << k)), nlev - h + k, w0,
+                         (uint32_t)parents, (const uint4*)cur, nxt, ctrs + k, blocks);
       HIP_TRY(hipGetLastError());
       std::swap(cur, nxt);
     }
-    const uint64_t nnodes = g.nroots << g.m;
+    const uint64_t nnodes = total << g.m;
     const uint32_t nq = ((nlev >> 4) + 1 + 3) / 4;  // uint4s holding rows 0 .. 8N of a t-vector
-    hipLaunchKernelGGL((k_range_tail_wide<(int)kRangeWideTail, MASK>), dim3((unsigned)grid_for(nnodes, p->cus)),
-                       dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig, dig_t, (const uint4*)np1, nlev - kRangeWideTail, w0,
-                       (uint32_t)nnodes, (const uint4*)cur, (uint32_t)g.skip, (uint32_t)n, ys, lam, (uint4*)tvec,
-                       (const uint4*)tpre, g.m, nq, ctrs + kRangeCtrs - 1, blocks);
+    hipLaunchKernelGGL((k_range_tail_wide<(int)tail, MASK, KP>), dim3((unsigned)grid_for(nnodes, p->cus)),
+                       dim3(kBlock), 0, st, p->d_tab, p->d_rk2, dig, dig_t, np1k, KP::make(nlev, (uint32_t)(g.nroots << g.m)),
+                       nlev - tail, w0, (uint32_t)nnodes, (const uint4*)cur, (uint32_t)g.skip, (uint32_t)n, ys, lam,
+                       (uint4*)tvec, (const uint4*)tpre, g.m, nq, ctrs + kRangeCtrs - 1, blocks);
     HIP_TRY(hipGetLastError());
   }
   if (!MASK)  // y[32, lambda) from the t-vectors (the existing tail kernels)
-    return run_tail(cwb, cwv, np1, s0, nlev, lam, 1, 0, tvec, n, ys, st, p->cus, n, party, w);
+    return run_tail(cwb, cwv, np1, s0, nlev, lam, K, key0, tvec, keys * n, ys, st, p->cus, n, party, w);
   return DCF_OK;
 }
 
@@ -2541,10 +2552,11 @@ static int range_wide_launch(dcf_prg* p, Lease& L, size_t nb, int party, const u
                      w->d_dig + (size_t)nlev * 64);
   HIP_TRY(hipGetLastError());
   phase_mark(p, L, 1);
-  const auto group = lam == 32 ? range_wide_group<true> : range_wide_group<false>;
+  const auto group = lam == 32 ? range_wide_group<true, RangeOneKey> : range_wide_group<false, RangeOneKey>;
   for (uint64_t o = 0; o < cnt; o += per) {  // h = 0: cnt < 2^12, one group
     const uint64_t n = std::min<uint64_t>(per, cnt - o);
-    if (int rc = group(p, L, nb, party, cwb, s0, range_add(A.x, off + o), n, h, ws, ys + o * (uint64_t)lam)) return rc;
+    if (int rc = group(p, L, nb, 1, party, cwb, s0, 0, 1, range_add(A.x, off + o), n, h, ws, ys + o * (uint64_t)lam))
+      return rc;
   }
   return range_end(p, L);
 }
@@ -2668,7 +2680,89 @@ size_t dcf_eval_range_keys_per_launch(size_t n_bytes, size_t num_keys, uint64_t 
   return (size_t)rangemk_keys_per_launch(rangemk_levels(n_bytes, std::max<size_t>(num_keys, 1), count), count);
 }
 
-// The slow path (lambda >= 32, N > 16): key by key, each gathered into the single-key
+// ---- K keys over the Hirose PRG at lambda >= 32, N <= 16 (kernels_range_wide.h under RangeDigKeys) ----
+
+// Height of the blocks (documented in include/dcf_hip.h): the single-key rule from 2^12 points per
+// key, where a key has at least 16 blocks of its own; below, the multi-key rule.
+static uint32_t rangemk_wide_levels(size_t n_bytes, uint64_t num_keys, uint64_t count) {
+  return count >= kRangeDirectMax ? range_levels(n_bytes, count) : rangemk_levels(n_bytes, num_keys, count);
+}
+
+// Whole keys per launch group at height h; 1 when the keys run one after another (a key of more
+// than kWideBatchPpk points, or one that exceeds a group alone).
+static uint64_t rangemk_wide_keys(size_t n_bytes, uint64_t count, uint32_t h) {
+  const uint64_t span = ((count >> h) + 2) << h;  // a key's leaves, clipped ones included, at most
+  if (count > kWideBatchPpk || span > range_wide_points(n_bytes)) return 1;
+  const uint64_t rpk = (count + kTailPts - 1) / kTailPts;  // launch_tail's grid rows per key (launch_tail2: 1)
+  const uint64_t kdig = std::max<uint64_t>(1, (0xFFFFFFFFull / 4u) / (8 * n_bytes));  // as eval_wide_batch
+  return std::max<uint64_t>(
+      1, std::min<uint64_t>({range_wide_points(n_bytes) / span, kWideBatchKeys, 8 * kWideBatchKeys / rpk, kdig}));
+}
+static bool rangemk_wide_grouped(size_t n_bytes, uint64_t count, uint32_t h) {
+  return count <= kWideBatchPpk && (((count >> h) + 2) << h) <= range_wide_points(n_bytes);
+}
+
+int dcf_eval_range_wide_multikey_subtree_levels(size_t n_bytes, size_t num_keys, uint64_t count) {
+  if (!n_bytes || n_bytes > 16 || !num_keys || !count) return 0;
+  return (int)rangemk_wide_levels(n_bytes, num_keys, count);
+}
+
+size_t dcf_eval_range_wide_keys_per_launch(size_t n_bytes, size_t lambda, size_t num_keys, uint64_t count) {
+  if (!n_bytes || n_bytes > 16 || !num_keys || !count || lambda < 32) return 0;
+  return (size_t)rangemk_wide_keys(n_bytes, count, rangemk_wide_levels(n_bytes, num_keys, count));
+}
+
+// The call: launch groups of whole keys under the per-lane key policy, or — when a group holds
+// less than a key — the keys one after another through the single-key kernels, each read in place
+// from the K-key block, with the groups of range_wide_launch.  On L.st throughout: no gather, no
+// buffer of the call's own, no stream wait.
+static int rangemk_wide(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb, const uint8_t* s0s,
+                        const RangeArg& A, uint64_t count, uint8_t* ys) {
+  hipStream_t st = L.st;
+  Workspace* w = L.w;
+  const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * nb);
+  const uint32_t h = rangemk_wide_levels(nb, K, count);
+  const bool grouped = rangemk_wide_grouped(nb, count, h);
+  const uint64_t per = range_wide_points(nb);
+  const uint64_t kp = grouped ? std::min<uint64_t>(K, rangemk_wide_keys(nb, count, h)) : 1;
+  const RangeWideWs ws =
+      range_wide_ws(std::min<uint64_t>(count, per), h, lam, kp, grouped ? kRangeWideTailKeys : kRangeWideTail);
+  if (w->dig_levels < kp * nlev) {  // dig_levels stays the size of the buffer, as eval_wide_batch keeps it
+    size_t have = (size_t)w->dig_levels * 65;
+    if (int rc = grow(&w->d_dig, &have, (size_t)kp * nlev * 65, st)) return rc;
+    w->dig_levels = (uint32_t)(kp * nlev);
+  }
+  if (int rc = range_begin(p, L, ws.total, true)) return rc;
+  phase_mark(p, L, 1);
+  const uint8_t* cwv = cwb + (size_t)nlev * K * lam;
+  const uint8_t* cwt = cwb + 2 * (size_t)nlev * K * lam;
+  const auto digest = [&](uint64_t k0, uint64_t nk) {  // key-major, dig_t behind the nk keys' rows
+    hipLaunchKernelGGL(k_cw_digest, dim3((unsigned)((4 * nlev * nk + 255) / 256)), dim3(256), 0, st, cwb, cwv, cwt, nlev,
+                       lam, (uint64_t)K, k0, (uint32_t)nk, (uint4*)w->d_dig, w->d_dig + (size_t)nk * nlev * 64);
+    return hipGetLastError();
+  };
+  if (grouped) {
+    const auto group = lam == 32 ? range_wide_group<true, RangeDigKeys> : range_wide_group<false, RangeDigKeys>;
+    for (uint64_t k0 = 0; k0 < K; k0 += kp) {
+      const uint64_t nk = std::min<uint64_t>(kp, K - k0);
+      HIP_TRY(digest(k0, nk));
+      if (int rc = group(p, L, nb, K, party, cwb, s0s, k0, nk, A.x, count, h, ws, ys + k0 * count * lam)) return rc;
+    }
+  } else {
+    const auto group = lam == 32 ? range_wide_group<true, RangeOneKey> : range_wide_group<false, RangeOneKey>;
+    for (uint64_t k = 0; k < K; ++k) {
+      HIP_TRY(digest(k, 1));
+      for (uint64_t o = 0; o < count; o += per) {
+        const uint64_t n = std::min<uint64_t>(per, count - o);
+        if (int rc = group(p, L, nb, K, party, cwb, s0s, k, 1, range_add(A.x, o), n, h, ws, ys + (k * count + o) * lam))
+          return rc;
+      }
+    }
+  }
+  return range_end(p, L);
+}
+
+// The slow path (the MMO PRG at lambda >= 32, N > 16): key by key, each gathered into the single-key
 // layout in a buffer of the call's own and run through the single-key range path.
 static int rangemk_fallback(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb,
                             const uint8_t* s0s, const RangeArg& A, uint64_t count, uint8_t* ys) {
@@ -2701,6 +2795,11 @@ int dcf_eval_range_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, 
   DeviceGuard dg(p->device);
   Lease L(p);
   if (int rc = L.order((hipStream_t)stream)) return rc;
+#ifndef DCF_RANGEMK_WIDE
+#define DCF_RANGEMK_WIDE 1  // A/B knob: 0 sends these shapes key by key through rangemk_fallback, as before
+#endif
+  if (DCF_RANGEMK_WIDE && p->kind == 0 && p->lambda >= 32 && n_bytes <= 16)
+    return rangemk_wide(p, L, n_bytes, num_keys, party, cwb, s0s, A, count, ys);
   if (p->lambda != 16 || n_bytes > 16)
     return rangemk_fallback(p, L, n_bytes, num_keys, party, cwb, s0s, A, count, ys);
   const uint32_t h = rangemk_levels(n_bytes, num_keys, count);

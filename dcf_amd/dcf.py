@@ -453,13 +453,27 @@ class DcfImpl:
         """Whole keys per launch group of eval_range_multikey_device (dcf_eval_range_keys_per_launch)."""
         return int(_lib.load().dcf_eval_range_keys_per_launch(self.n_bytes, int(num_keys), int(count)))
 
+    def range_wide_multikey_subtree_levels(self, num_keys: int, count: int) -> int:
+        """Height h of the aligned blocks eval_range_multikey_device expands with the Hirose PRG at
+        LAMBDA >= 32, N <= 16 (dcf_eval_range_wide_multikey_subtree_levels; the rule is in
+        include/dcf_hip.h); 0 for a shape that path does not take."""
+        return int(_lib.load().dcf_eval_range_wide_multikey_subtree_levels(self.n_bytes, int(num_keys), int(count)))
+
+    def range_wide_keys_per_launch(self, num_keys: int, count: int) -> int:
+        """Whole keys per launch group of that path (dcf_eval_range_wide_keys_per_launch); 0 for a
+        shape it does not take."""
+        return int(_lib.load().dcf_eval_range_wide_keys_per_launch(self.n_bytes, self.lam, int(num_keys), int(count)))
+
     def eval_range_multikey_device(self, b: bool, cwb, s0s, x0, count: int, ys=None):
         """K keys over one range: `Dcf::eval` of key k at x0 + i for i in [0, count), as a
         (K, count, LAMBDA) device tensor.  cwb: the K-key block of gen_batch_device, s0s (K, LAMBDA).
         LAMBDA = 16, N <= 16: one tree expansion over all keys, 2 AES-256 blocks per output with the
-        Hirose PRG, 4 AES-128 blocks with the MMO PRG; asynchronous on the current stream for both.
-        LAMBDA >= 32 goes key by key through eval_range_device's path (the Hirose tree expansion at
-        N <= 16) and waits for the stream."""
+        Hirose PRG, 4 AES-128 blocks with the MMO PRG.  Hirose PRG, LAMBDA >= 32, N <= 16: one tree
+        expansion of bytes [0, 32) over the keys of a launch group (range_wide_keys_per_launch of
+        them, blocks of height range_wide_multikey_subtree_levels), 4 AES-256 blocks per output, and
+        the linear tail for bytes [32, LAMBDA).  All three are asynchronous on the current stream.
+        The MMO PRG at LAMBDA >= 32 and N > 16 go key by key through eval_range_device's path and
+        wait for the stream."""
         import torch
         lam, nb, dev = self.lam, self.n_bytes, self.prg.device
         xb = self._x0(x0)

@@ -262,6 +262,13 @@ class DcfImpl final : public Dcf<N, LAMBDA> {
   static size_t range_keys_per_launch(size_t num_keys, uint64_t count) {
     return dcf_eval_range_keys_per_launch(N, num_keys, count);
   }
+  // The same two for the Hirose PRG at LAMBDA >= 32, N <= 16 (0: not that path).
+  static int range_wide_multikey_subtree_levels(size_t num_keys, uint64_t count) {
+    return dcf_eval_range_wide_multikey_subtree_levels(N, num_keys, count);
+  }
+  static size_t range_wide_keys_per_launch(size_t num_keys, uint64_t count) {
+    return dcf_eval_range_wide_keys_per_launch(N, LAMBDA, num_keys, count);
+  }
 
  private:
   const PrgT& prg_;

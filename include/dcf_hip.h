@@ -428,10 +428,28 @@ uint64_t dcf_eval_range_wide_points_per_launch(size_t n_bytes, size_t lambda);
  *   (key, point) pairs.  Asynchronous on `stream` like the Hirose path: no key-by-key gather, no
  *   stream wait.  dcf_prg_last_eval_blocks then reports the executed AES-128 blocks,
  *   keys * nroots (2 (8N - h) + 4 (2^h - 1)) per group, and 2 * 8N * K * count at h = 0.
- *   Otherwise (lambda >= 32, N > 16) — key by key: each key is gathered into the single-key
- *   layout in a buffer of the call's own and run through dcf_eval_range_device's path, so the
- *   Hirose PRG at lambda >= 32, N <= 16 gets that path's tree expansion for every key; the call
- *   still goes key by key and still waits for the stream before it returns.
+ *   Hirose PRG, lambda >= 32, N <= 16 (kernels_range_wide.h under a per-lane key policy): one tree
+ *   expansion over the keys of a launch group, blocks of height
+ *   h = dcf_eval_range_wide_multikey_subtree_levels.  The keys * nroots roots are walked one lane
+ *   each from their keys' seeds, the levels below are expanded breadth-first over all keys at once
+ *   on 80-byte rows (the keys one after another in every node buffer, each in leaf order; node j of
+ *   a level with `per` nodes per key is node j - key * per of key j / per) and the last level in
+ *   registers; the correction words come per lane from the key-major CW digest of the group.  Leaf
+ *   g of a key is its output g - skip: y[0:32) and, when lambda > 32, the t-vector go to row
+ *   key * count + (g - skip) of the group, from which the existing tail kernels write
+ *   y[32, lambda) with count points per key.  h = 0: one root walk over the keys * count (key,
+ *   point) pairs.  Indices are 32-bit within a launch group of
+ *   dcf_eval_range_wide_keys_per_launch whole keys; only the key offset is 64-bit.  When count >
+ *   32768, or one key alone exceeds a group, the keys run one after another through the
+ *   single-key kernels, each read in place from the K-key block, in dcf_eval_range_device's
+ *   launch groups.  One workspace allocation holds a group's t-vectors, node buffers (80 B per
+ *   two outputs), root prefixes and counters; the digest is keys * 8N * 65 bytes.  Asynchronous on
+ *   `stream`: no gather, no buffer of the call's own, no stream wait.  dcf_prg_last_eval_blocks
+ *   then reports the executed AES-256 blocks, exactly
+ *     sum over groups of keys * nroots * (4 (8N - h) + 4 (2^h - 1)),   4 * 8N * K * count at h = 0.
+ *   Otherwise (the MMO PRG at lambda >= 32, N > 16) — key by key: each key is gathered into the
+ *   single-key layout in a buffer of the call's own and run through dcf_eval_range_device's path;
+ *   the call waits for the stream before it returns.
  * Errors, nothing launched: null prg / cwb / s0s / x0, null ys with work to do, bad party ->
  * DCF_ERR_ARG; n_bytes == 0 -> DCF_ERR_N; N > 256 -> DCF_ERR_UNSUPPORTED; x0 + count > 2^(8N) ->
  * DCF_ERR_ARG.  num_keys == 0 or count == 0 -> DCF_OK, nothing written. */
@@ -453,6 +471,27 @@ int dcf_eval_range_multikey_subtree_levels(size_t n_bytes, size_t num_keys, uint
  * 2^28 (every key has at most (count >> h) + 2 blocks), at least 1; num_keys enters through h
  * only.  1 also when one key alone exceeds a launch. */
 size_t dcf_eval_range_keys_per_launch(size_t n_bytes, size_t num_keys, uint64_t count);
+
+/* Height h of the aligned blocks dcf_eval_range_multikey_device uses on the Hirose PRG at
+ * lambda >= 32, N <= 16 (pure arithmetic, no device access):
+ *   count >= 2^12:  dcf_eval_range_subtree_levels(n_bytes, count) — a key has at least 16 blocks of
+ *                   its own, and the call executes exactly the blocks of the K single-key calls;
+ *   count <  2^12:  dcf_eval_range_multikey_subtree_levels(n_bytes, num_keys, count) — where the
+ *                   single-key rule would walk every point of every key from the root.
+ * 0 for a shape that path does not take (n_bytes == 0, n_bytes > 16, num_keys == 0) and for
+ * count == 0. */
+int dcf_eval_range_wide_multikey_subtree_levels(size_t n_bytes, size_t num_keys, uint64_t count);
+
+/* Whole keys per launch group of that path at that height h: the most keys such that
+ *   keys * (((count >> h) + 2) << h) <= dcf_eval_range_wide_points_per_launch(n_bytes, lambda)
+ *     (every key has at most (count >> h) + 2 blocks: the t-vector bound, 2^22),
+ *   keys <= 4096, and keys * ceil(count / 4096) <= 32768 (the grid rows of the kernels that write
+ *     y[32, lambda): one row per key and 4096 points, as dcf_eval_multikey_device keeps them),
+ *   4 * keys * 8N < 2^32 (the CW digest's 32-bit index),
+ * at least 1; num_keys enters through h only.  1 when count > 32768 or one key alone exceeds a
+ * group: the keys then run one after another.  0 for a shape that path does not take
+ * (n_bytes == 0, n_bytes > 16, num_keys == 0, lambda < 32) and for count == 0. */
+size_t dcf_eval_range_wide_keys_per_launch(size_t n_bytes, size_t lambda, size_t num_keys, uint64_t count);
 
 #ifdef __cplusplus
 }

@@ -84,4 +84,6 @@ extern "C" {
                                           stream: *mut c_void) -> c_int;
     pub fn dcf_eval_range_multikey_subtree_levels(n_bytes: usize, num_keys: usize, count: u64) -> c_int;
     pub fn dcf_eval_range_keys_per_launch(n_bytes: usize, num_keys: usize, count: u64) -> usize;
+    pub fn dcf_eval_range_wide_multikey_subtree_levels(n_bytes: usize, num_keys: usize, count: u64) -> c_int;
+    pub fn dcf_eval_range_wide_keys_per_launch(n_bytes: usize, lambda: usize, num_keys: usize, count: u64) -> usize;
 }

@@ -186,6 +186,19 @@ impl<const N: usize, const LAMBDA: usize> DcfHip<N, LAMBDA> {
     pub fn range_keys_per_launch(num_keys: usize, count: u64) -> usize {
         unsafe { ffi::dcf_eval_range_keys_per_launch(N, num_keys, count) }
     }
+
+    /// Height of the aligned blocks `eval_range_multikey_device` expands with the Hirose PRG at
+    /// `LAMBDA >= 32`, `N <= 16` (`dcf_eval_range_wide_multikey_subtree_levels`); 0 for a shape that
+    /// path does not take.
+    pub fn range_wide_multikey_subtree_levels(num_keys: usize, count: u64) -> i32 {
+        unsafe { ffi::dcf_eval_range_wide_multikey_subtree_levels(N, num_keys, count) }
+    }
+
+    /// Whole keys per launch group of that path (`dcf_eval_range_wide_keys_per_launch`); 0 for a
+    /// shape it does not take.
+    pub fn range_wide_keys_per_launch(num_keys: usize, count: u64) -> usize {
+        unsafe { ffi::dcf_eval_range_wide_keys_per_launch(N, LAMBDA, num_keys, count) }
+    }
 }
 
 impl<const N: usize, const LAMBDA: usize> Dcf<N, LAMBDA> for DcfHip<N, LAMBDA> {

@@ -1,10 +1,13 @@
 """Multi-key contiguous-range eval (dcf_eval_range_multikey_device) on one MI355X, Hirose or MMO PRG
-(--prg), LAMBDA = 16, keys from gen_batch_device.
+(--prg), LAMBDA = 16 or --lam, keys from gen_batch_device.
 
 Shapes:
-  N = 1  whole domain (256 points),            K = 2^20
-  N = 2  whole domain (2^16 points),           K = 2^12
-  N = 16 count = 2^12 at a random odd x0,      K = 2^12
+  n1     N = 1  whole domain (256 points),            K = 2^20
+  n2     N = 2  whole domain (2^16 points),           K = 2^12
+  n16    N = 16 count = 2^12 at a random odd x0,      K = 2^12
+  w1a    N = 1  whole domain,                         K = 2^12   (the LAMBDA >= 32 shapes: --lam 128
+  w1b    N = 1  whole domain,                         K = 2^16    for w1a / w1b, --lam 32 for w2)
+  w2     N = 2  count = 1000 at a random odd x0,      K = 2^12
 For each: outputs/s, AES blocks per output (dcf_prg_last_eval_blocks, counted on the device) and the
 executed blocks/s as a fraction of the T-table LDS bound (256 CUs x 32 lookups/clk x 2.4 GHz over the
 lookups of a block: 224 for AES-256, 87.77e9 blocks/s, Hirose; 160 for AES-128, 122.88e9, MMO).  Baselines in the same
@@ -18,8 +21,8 @@ Every figure is the median of REPS >= 10 repetitions timed one by one with HIP e
 untimed ones; min and max are kept beside it.  Prints one JSON document and writes it to --out
 (default profiles/range_multikey_bench.json, range_multikey_bench_mmo.json with --prg mmo).
 
-  python scripts/range_multikey_bench.py [--prg hirose|mmo] [--out FILE] [--reps 10] [--warmup 3] [--shapes n1,n2,n16] [--loop-keys 4096]
-                                         [--max-keys K]
+  python scripts/range_multikey_bench.py [--prg hirose|mmo] [--lam 16] [--out FILE] [--reps 10] [--warmup 3]
+                                         [--shapes n1,n2,n16] [--loop-keys 4096] [--max-keys K]
 """
 import argparse
 import json
@@ -40,6 +43,9 @@ SHAPES = {  # name: (N, count or None for the whole domain, K)
     "n1": (1, None, 1 << 20),
     "n2": (2, None, 1 << 12),
     "n16": (16, 1 << 12, 1 << 12),
+    "w1a": (1, None, 1 << 12),
+    "w1b": (1, None, 1 << 16),
+    "w2": (2, 1000, 1 << 12),
 }
 
 
@@ -87,6 +93,7 @@ def spread_apart(fast, slow):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--prg", choices=("hirose", "mmo"), default="hirose")
+    ap.add_argument("--lam", type=int, default=16, help="LAMBDA (a multiple of 16)")
     ap.add_argument("--out")
     ap.add_argument("--loop-keys", type=int, default=1 << 12)
     ap.add_argument("--max-keys", type=int, help="cap every shape's K (a library whose path runs key by key)")
@@ -98,13 +105,14 @@ def main():
     a.out = a.out or os.path.join("profiles", "range_multikey_bench.json" if a.prg == "hirose"
                                   else f"range_multikey_bench_{a.prg}.json")
     LDS_BOUND_BLOCKS_PER_S, LOOP_KEYS_MAX = LDS_LOOKUPS_PER_S / LDS_PER_BLOCK[a.prg], a.loop_keys
-    lam = 16
+    lam = a.lam
     rng = np.random.default_rng(0x7B)
     if a.prg == "mmo":
-        prg = dcf_amd.Aes128MatyasMeyerOseasPrg([rng.bytes(16) for _ in range(4)], lam)
+        prg = dcf_amd.Aes128MatyasMeyerOseasPrg([rng.bytes(16) for _ in range(4 * lam // 16)], lam)
     else:
-        prg = dcf_amd.Aes256HirosePrg([rng.bytes(32) for _ in range(2)], lam)
-    res = {"device": torch.cuda.get_device_name(0), "prg": a.prg, "library": dcf_amd.load().dcf_version().decode(),
+        prg = dcf_amd.Aes256HirosePrg([rng.bytes(32) for _ in range(2 if lam == 16 else 18)], lam)
+    wide = a.prg == "hirose" and lam >= 32  # the LAMBDA >= 32 tree path has its own height and group size
+    res = {"device": torch.cuda.get_device_name(0), "prg": a.prg, "lambda": lam, "library": dcf_amd.load().dcf_version().decode(),
            "lds_bound_blocks_per_s": LDS_BOUND_BLOCKS_PER_S, "loop_keys_max": LOOP_KEYS_MAX, "shapes": []}
     g = torch.Generator(device="cuda").manual_seed(0x7B)
     rnd = lambda *shape: torch.randint(0, 256, shape, dtype=torch.uint8, device="cuda", generator=g)  # noqa: E731
@@ -115,8 +123,10 @@ def main():
         d = dcf_amd.DcfImpl(nb, lam, prg)
         if count is None:
             x0, count = 0, 1 << (8 * nb)
-        else:
+        elif nb == 16:
             x0 = (int.from_bytes(rng.bytes(8), "big") << 64) | (int.from_bytes(rng.bytes(7), "big") | 1)
+        else:
+            x0 = int(rng.integers(0, ((1 << (8 * nb)) - count) // 2)) * 2 + 1
         alpha, s0 = rnd(K, nb), rnd(K, lam)
         if nb == 16:  # alphas inside the range
             alpha = points(x0, count, nb)[torch.randint(0, count, (K,), device="cuda", generator=g)].contiguous()
@@ -148,8 +158,9 @@ def main():
 
         sec = t["median_ms"] * 1e-3
         row = {"shape": name, "n_bytes": nb, "num_keys": K, "count": count, "x0": hex(x0),
-               "subtree_levels": d.range_multikey_subtree_levels(K, count),
-               "keys_per_launch": d.range_keys_per_launch(K, count),
+               "subtree_levels": (d.range_wide_multikey_subtree_levels if wide and nb <= 16
+                                  else d.range_multikey_subtree_levels)(K, count),
+               "keys_per_launch": (d.range_wide_keys_per_launch if wide and nb <= 16 else d.range_keys_per_launch)(K, count),
                "multikey": t, "outputs_per_s": total / sec,
                "blocks": blocks, "blocks_per_output": blocks / total, "blocks_per_s": blocks / sec,
                "lds_bound_frac": blocks / sec / LDS_BOUND_BLOCKS_PER_S,

@@ -38,6 +38,7 @@ EXPORTS = [
     "dcf_eval_range_multikey_device", "dcf_eval_range_multikey_subtree_levels", "dcf_eval_range_keys_per_launch",
     "dcf_eval_range_wide_points_per_launch", "dcf_prefix_deepen_calls", "dcf_prefix_reuse_max_depth",
     "dcf_eval_range_wide_multikey_subtree_levels", "dcf_eval_range_wide_keys_per_launch",
+    "dcf_eval_range_fold_device", "dcf_eval_range_fold_multikey_device",
 ]
 
 
@@ -98,6 +99,8 @@ def load(path: str = LIB_PATH):
         "dcf_eval_range_keys_per_launch": ([sz, sz, ctypes.c_uint64], sz),
         "dcf_eval_range_wide_multikey_subtree_levels": ([sz, sz, ctypes.c_uint64], i),
         "dcf_eval_range_wide_keys_per_launch": ([sz, sz, sz, ctypes.c_uint64], sz),
+        "dcf_eval_range_fold_device": ([vp, sz, i, u8p, u8p, u8p, ctypes.c_uint64, u8p, u8p, vp], i),
+        "dcf_eval_range_fold_multikey_device": ([vp, sz, sz, i, u8p, u8p, u8p, ctypes.c_uint64, u8p, u8p, vp], i),
         "dcf_share_bincode_bytes": ([sz, sz, sz], sz),
         "dcf_share_to_bincode": ([sz, sz, u8p, u8p, sz, u8p, sz], i),
         "dcf_share_from_bincode": ([sz, sz, u8p, sz, u8p, u8p, sz, ctypes.POINTER(sz)], i),

@@ -121,6 +121,8 @@ struct Workspace {
   size_t mkey_bytes = 0;
   uint32_t* d_tctr = nullptr; // LAMBDA >= 32 paired-slot tail with LDS-filling tables: per-workgroup block counters
   size_t tctr_bytes = 0;
+  uint8_t* d_fold = nullptr;  // range fold, the shapes without a folding tail: a pass of range outputs (and one gathered key)
+  size_t fold_bytes = 0;
   // Host-pointer entry points: three non-blocking streams (copy-in, compute, copy-out), their
   // events and staging (pinned host + device), grown on demand and kept.
   hipStream_t hs[3] = {nullptr, nullptr, nullptr};
@@ -1194,7 +1196,7 @@ static void free_workspace(Workspace* w) {
   if (w->aux) (void)hipStreamSynchronize(w->aux);
   if (w->pending) (void)hipEventSynchronize(w->done);  // the last device call's kernels
   for (void* b : {(void*)w->d_ctr, (void*)w->d_ws, (void*)w->d_dig, (void*)w->d_kdig, (void*)w->d_pfx,
-                  (void*)w->d_mkey, (void*)w->d_stage, (void*)w->d_tctr, (void*)w->d_pst})
+                  (void*)w->d_mkey, (void*)w->d_stage, (void*)w->d_tctr, (void*)w->d_pst, (void*)w->d_fold})
     if (b) (void)hipFree(b);
   if (w->h_stage) (void)hipHostFree(w->h_stage);
   if (w->h_tiny) (void)hipHostFree(w->h_tiny);
@@ -1267,7 +1269,7 @@ size_t dcf_prg_device_bytes(const dcf_prg* p) {
     if (w->d_ctr) b += kCtrBytes;
     if (w->d_pst) b += kPfxStateBytes;
     b += (size_t)w->dig_levels * 65 + w->kdig_bytes + w->ws_bytes + w->pfx_bytes +
-         w->d_stage_bytes + w->mkey_bytes + w->tctr_bytes;
+         w->d_stage_bytes + w->mkey_bytes + w->tctr_bytes + w->fold_bytes;
   }
   return b;
 }
@@ -2384,10 +2386,12 @@ static int range_end(dcf_prg* p, Lease& L) {
 // [k * n, (k + 1) * n) of ys (several keys in a group: n is the call's count).  PRG: the prg's PRG
 // policy, RangeHirose or RangeMmo.  KP: the kernels' key policy — RangeOneKey takes key0 = 0,
 // keys = K = 1.  The caller has sized the workspace (range_ws_bytes) and zeroed the block count.
-extern "C++" template <class PRG, class KP>
+// OUT: the tail's output policy; under RangeFold (h > 0 only) ys is row key0 of the call's `out`,
+// 16 bytes per key, zeroed by the caller, and op holds the group's rows of the table.
+extern "C++" template <class PRG, class KP, class OUT>
 static int range_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb, const uint8_t* s0s,
                        uint64_t key0, uint64_t keys, const RangeX xa, uint64_t n, uint32_t h, size_t buf_bytes,
-                       uint8_t* ys) {
+                       uint8_t* ys, const OUT op) {
   using Idx = typename KP::Idx;
   hipStream_t st = L.st;
   Workspace* w = L.w;
@@ -2404,6 +2408,7 @@ static int range_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, con
     return dim3((unsigned)std::min<uint64_t>((uint64_t)p->cus, (total + PRG::kRootsPer - 1) / PRG::kRootsPer));
   };
   if (h == 0) {  // every point is its own root: the root walk writes y
+    if (OUT::kFold) return fail(DCF_ERR_ARG, "range fold: the root walk has no fold");
     const uint64_t total = keys * n;
     hipLaunchKernelGGL((PRG::template roots<true, KP>()), roots_grid(total), dim3(kBlock), 0, st, p->d_tab, rk, cws, cwv,
                        cwt, np1, s0, KP::make(K, (uint32_t)n), (uint32_t)party, xa, nlev, (Idx)total, (uint4*)ys, blocks);
@@ -2429,10 +2434,10 @@ static int range_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, con
     std::swap(cur, nxt);
   }
   const uint64_t nnodes = total << g.m;
-  hipLaunchKernelGGL((k_range_tail16<(int)kFdTail, PRG, KP>), dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock), 0,
-                     st, p->d_tab, rk, cws, cwv, cwt, np1, KP::make(K, (uint32_t)(g.nroots << g.m)), nlev - kFdTail,
+  hipLaunchKernelGGL((k_range_tail16<(int)kFdTail, PRG, KP, OUT>), dim3((unsigned)grid_for(nnodes, p->cus)), dim3(kBlock),
+                     0, st, p->d_tab, rk, cws, cwv, cwt, np1, KP::make(K, (uint32_t)(g.nroots << g.m)), nlev - kFdTail,
                      (uint32_t)nnodes, (const uint4*)cur, (uint32_t)g.skip, (uint32_t)n, (uint4*)ys,
-                     ctrs + kRangeCtrs - 1, blocks);
+                     ctrs + kRangeCtrs - 1, blocks, op);
   HIP_TRY(hipGetLastError());
   return DCF_OK;
 }
@@ -2561,6 +2566,28 @@ static int range_wide_launch(dcf_prg* p, Lease& L, size_t nb, int party, const u
   return range_end(p, L);
 }
 
+// The tree path at lambda = 16, N <= 16, on L.st: points [off, off + cnt) of the range in launch
+// groups of 2^28.  RangeStore: into ys (the output of point `off`).  RangeFold (h > 0): all groups
+// into the one row ys of 16 bytes, which the caller has zeroed; op holds the table from point `off`.
+extern "C++" template <class OUT>
+static int range_tree(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
+                      const RangeArg& A, uint64_t off, uint64_t cnt, uint32_t h, uint8_t* ys, bool zero_blocks,
+                      const OUT op) {
+  size_t buf_bytes;
+  const size_t ws = range_ws_bytes(1, std::min<uint64_t>(cnt, kRangeLaunch), h, &buf_bytes);
+  if (int rc = range_begin(p, L, ws, zero_blocks)) return rc;
+  phase_mark(p, L, 1);
+  const auto group =
+      p->kind == 0 ? range_group<RangeHirose, RangeOneKey, OUT> : range_group<RangeMmo, RangeOneKey, OUT>;
+  for (uint64_t o = 0; o < cnt; o += kRangeLaunch) {  // h = 0: cnt < 2^12, one pass
+    const uint64_t n = std::min<uint64_t>(kRangeLaunch, cnt - o);
+    if (int rc = group(p, L, nb, 1, party, cwb, s0, 0, 1, range_add(A.x, off + o), n, h, buf_bytes,
+                       OUT::kFold ? ys : ys + o * 16, op.at(o)))
+      return rc;
+  }
+  return range_end(p, L);
+}
+
 // Points [off, off + cnt) of the range into ys (the output of point `off`), on L.st.  h: the
 // call's block height (range_levels of its whole count).  zero_blocks: first part of a call.
 static int range_launch(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
@@ -2581,16 +2608,7 @@ static int range_launch(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_
     HIP_TRY(hipStreamSynchronize(st));  // xs is freed on return
     return DCF_OK;
   }
-  size_t buf_bytes;
-  const size_t ws = range_ws_bytes(1, std::min<uint64_t>(cnt, kRangeLaunch), h, &buf_bytes);
-  if (int rc = range_begin(p, L, ws, zero_blocks)) return rc;
-  phase_mark(p, L, 1);
-  const auto group = p->kind == 0 ? range_group<RangeHirose, RangeOneKey> : range_group<RangeMmo, RangeOneKey>;
-  for (uint64_t o = 0; o < cnt; o += kRangeLaunch) {  // h = 0: cnt < 2^12, one pass
-    const uint64_t n = std::min<uint64_t>(kRangeLaunch, cnt - o);
-    if (int rc = group(p, L, nb, 1, party, cwb, s0, 0, 1, range_add(A.x, off + o), n, h, buf_bytes, ys + o * lam)) return rc;
-  }
-  return range_end(p, L);
+  return range_tree(p, L, nb, party, cwb, s0, A, off, cnt, h, ys, zero_blocks, RangeStore{});
 }
 
 int dcf_eval_range_device(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
@@ -2715,16 +2733,18 @@ size_t dcf_eval_range_wide_keys_per_launch(size_t n_bytes, size_t lambda, size_t
 // The call: launch groups of whole keys under the per-lane key policy, or — when a group holds
 // less than a key — the keys one after another through the single-key kernels, each read in place
 // from the K-key block, with the groups of range_wide_launch.  On L.st throughout: no gather, no
-// buffer of the call's own, no stream wait.
-static int rangemk_wide(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb, const uint8_t* s0s,
-                        const RangeArg& A, uint64_t count, uint8_t* ys) {
+// buffer of the call's own, no stream wait.  Keys [key0, key0 + nkeys) of the K-key block into ys (the
+// first output of key key0); zero_blocks: first part of a call.
+static int rangemk_wide(dcf_prg* p, Lease& L, size_t nb, size_t K, uint64_t key0, uint64_t nkeys, int party,
+                        const uint8_t* cwb, const uint8_t* s0s, const RangeArg& A, uint64_t count, uint8_t* ys,
+                        bool zero_blocks) {
   hipStream_t st = L.st;
   Workspace* w = L.w;
   const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * nb);
-  const uint32_t h = rangemk_wide_levels(nb, K, count);
+  const uint32_t h = rangemk_wide_levels(nb, nkeys, count);
   const bool grouped = rangemk_wide_grouped(nb, count, h);
   const uint64_t per = range_wide_points(nb);
-  const uint64_t kp = grouped ? std::min<uint64_t>(K, rangemk_wide_keys(nb, count, h)) : 1;
+  const uint64_t kp = grouped ? std::min<uint64_t>(nkeys, rangemk_wide_keys(nb, count, h)) : 1;
   const RangeWideWs ws =
       range_wide_ws(std::min<uint64_t>(count, per), h, lam, kp, grouped ? kRangeWideTailKeys : kRangeWideTail);
   if (w->dig_levels < kp * nlev) {  // dig_levels stays the size of the buffer, as eval_wide_batch keeps it
@@ -2732,7 +2752,7 @@ static int rangemk_wide(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, co
     if (int rc = grow(&w->d_dig, &have, (size_t)kp * nlev * 65, st)) return rc;
     w->dig_levels = (uint32_t)(kp * nlev);
   }
-  if (int rc = range_begin(p, L, ws.total, true)) return rc;
+  if (int rc = range_begin(p, L, ws.total, zero_blocks)) return rc;
   phase_mark(p, L, 1);
   const uint8_t* cwv = cwb + (size_t)nlev * K * lam;
   const uint8_t* cwt = cwb + 2 * (size_t)nlev * K * lam;
@@ -2743,18 +2763,20 @@ static int rangemk_wide(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, co
   };
   if (grouped) {
     const auto group = lam == 32 ? range_wide_group<true, RangeDigKeys> : range_wide_group<false, RangeDigKeys>;
-    for (uint64_t k0 = 0; k0 < K; k0 += kp) {
-      const uint64_t nk = std::min<uint64_t>(kp, K - k0);
+    for (uint64_t k0 = key0; k0 < key0 + nkeys; k0 += kp) {
+      const uint64_t nk = std::min<uint64_t>(kp, key0 + nkeys - k0);
       HIP_TRY(digest(k0, nk));
-      if (int rc = group(p, L, nb, K, party, cwb, s0s, k0, nk, A.x, count, h, ws, ys + k0 * count * lam)) return rc;
+      if (int rc = group(p, L, nb, K, party, cwb, s0s, k0, nk, A.x, count, h, ws, ys + (k0 - key0) * count * lam))
+        return rc;
     }
   } else {
     const auto group = lam == 32 ? range_wide_group<true, RangeOneKey> : range_wide_group<false, RangeOneKey>;
-    for (uint64_t k = 0; k < K; ++k) {
+    for (uint64_t k = key0; k < key0 + nkeys; ++k) {
       HIP_TRY(digest(k, 1));
       for (uint64_t o = 0; o < count; o += per) {
         const uint64_t n = std::min<uint64_t>(per, count - o);
-        if (int rc = group(p, L, nb, K, party, cwb, s0s, k, 1, range_add(A.x, o), n, h, ws, ys + (k * count + o) * lam))
+        if (int rc = group(p, L, nb, K, party, cwb, s0s, k, 1, range_add(A.x, o), n, h, ws,
+                           ys + ((k - key0) * count + o) * lam))
           return rc;
       }
     }
@@ -2763,9 +2785,11 @@ static int rangemk_wide(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, co
 }
 
 // The slow path (the MMO PRG at lambda >= 32, N > 16): key by key, each gathered into the single-key
-// layout in a buffer of the call's own and run through the single-key range path.
-static int rangemk_fallback(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb,
-                            const uint8_t* s0s, const RangeArg& A, uint64_t count, uint8_t* ys) {
+// layout in a buffer of the call's own and run through the single-key range path.  Keys
+// [key0, key0 + nkeys) of the K-key block into ys (the first output of key key0).
+static int rangemk_fallback(dcf_prg* p, Lease& L, size_t nb, size_t K, uint64_t key0, uint64_t nkeys, int party,
+                            const uint8_t* cwb, const uint8_t* s0s, const RangeArg& A, uint64_t count, uint8_t* ys,
+                            bool zero_blocks) {
   const size_t lam = p->lambda;
   const size_t kb = align256(dcf_cwb_bytes(nb, lam, 1));
   DevBuf key;  // range_launch's eval owns the workspace
@@ -2774,14 +2798,65 @@ static int rangemk_fallback(dcf_prg* p, Lease& L, size_t nb, size_t K, int party
   HIP_TRY(hipMemsetAsync(dk, 0, kb + lam, L.st));
   const uint8_t* np1 = cwb + dcf_cwb_np1_offset(nb, lam, K);
   const uint32_t h = range_levels(nb, count);
-  for (uint64_t k = 0; k < K; ++k) {
+  for (uint64_t k = key0; k < key0 + nkeys; ++k) {
     hipLaunchKernelGGL(k_rangemk_gather, dim3(8), dim3(256), 0, L.st, cwb, np1, s0s, (uint64_t)K, k,
                        (uint32_t)(8 * nb), (uint32_t)lam, (uint32_t)dcf_cwb_np1_offset(nb, lam, 1), dk, dk + kb);
     HIP_TRY(hipGetLastError());
-    if (int rc = range_launch(p, L, nb, party, dk, dk + kb, A, 0, count, h, ys + k * count * lam, k == 0)) return rc;
+    if (int rc = range_launch(p, L, nb, party, dk, dk + kb, A, 0, count, h, ys + (k - key0) * count * lam,
+                              zero_blocks && k == key0))
+      return rc;
   }
   HIP_TRY(hipStreamSynchronize(L.st));  // `key` is freed on return
   return DCF_OK;
+}
+
+// The tree path at lambda = 16, N <= 16, on L.st: keys [key0, key0 + nkeys) of the K-key block in
+// launch groups of whole keys (or of 2^28 outputs of one key) at block height h.  RangeStore: into
+// ys, the first output of key key0.  RangeFold (h > 0): ys is row key0 of the call's `out`, 16
+// bytes per key, zeroed by the caller: the groups of one key fold into the same row.
+extern "C++" template <class OUT>
+static int rangemk_tree(dcf_prg* p, Lease& L, size_t nb, size_t K, uint64_t key0, uint64_t nkeys, int party,
+                        const uint8_t* cwb, const uint8_t* s0s, const RangeArg& A, uint64_t count, uint32_t h,
+                        uint8_t* ys, bool zero_blocks, const OUT op) {
+  const uint64_t per = std::min<uint64_t>(nkeys, rangemk_keys_per_launch(h, count));
+  const uint64_t row = OUT::kFold ? 1 : count;  // rows of ys per key
+  size_t buf_bytes;
+  const size_t ws = range_ws_bytes(per, std::min<uint64_t>(count, kRangeLaunch), h, &buf_bytes);
+  if (int rc = range_begin(p, L, ws, zero_blocks)) return rc;
+  phase_mark(p, L, 1);
+  const auto group = p->kind == 0 ? range_group<RangeHirose, RangeKeys, OUT> : range_group<RangeMmo, RangeKeys, OUT>;
+  if ((count >> h) + 2 <= (kRangeLaunch >> h)) {  // groups of whole keys
+    for (uint64_t k0 = key0; k0 < key0 + nkeys; k0 += per) {
+      const uint64_t keys = std::min<uint64_t>(per, key0 + nkeys - k0);
+      if (int rc = group(p, L, nb, K, party, cwb, s0s, k0, keys, A.x, count, h, buf_bytes, ys + (k0 - key0) * row * 16, op))
+        return rc;
+    }
+  } else {  // one key alone exceeds a launch: the keys one after another, 2^28 outputs at a time
+    for (uint64_t k = key0; k < key0 + nkeys; ++k)
+      for (uint64_t o = 0; o < count; o += kRangeLaunch) {
+        const uint64_t n = std::min<uint64_t>(kRangeLaunch, count - o);
+        if (int rc = group(p, L, nb, K, party, cwb, s0s, k, 1, range_add(A.x, o), n, h, buf_bytes,
+                           ys + ((k - key0) * row + (OUT::kFold ? 0 : o)) * 16, op.at(o)))
+          return rc;
+      }
+  }
+  return range_end(p, L);
+}
+
+// dcf_eval_range_multikey_device's paths over keys [key0, key0 + nkeys) of the K-key block, into ys
+// (the first output of key key0), on L.st; the heights and groups are those of a call of nkeys keys.
+static int rangemk_run(dcf_prg* p, Lease& L, size_t nb, size_t K, uint64_t key0, uint64_t nkeys, int party,
+                       const uint8_t* cwb, const uint8_t* s0s, const RangeArg& A, uint64_t count, uint8_t* ys,
+                       bool zero_blocks) {
+#ifndef DCF_RANGEMK_WIDE
+#define DCF_RANGEMK_WIDE 1  // A/B knob: 0 sends these shapes key by key through rangemk_fallback, as before
+#endif
+  if (DCF_RANGEMK_WIDE && p->kind == 0 && p->lambda >= 32 && nb <= 16)
+    return rangemk_wide(p, L, nb, K, key0, nkeys, party, cwb, s0s, A, count, ys, zero_blocks);
+  if (p->lambda != 16 || nb > 16)
+    return rangemk_fallback(p, L, nb, K, key0, nkeys, party, cwb, s0s, A, count, ys, zero_blocks);
+  return rangemk_tree(p, L, nb, K, key0, nkeys, party, cwb, s0s, A, count, rangemk_levels(nb, nkeys, count), ys,
+                      zero_blocks, RangeStore{});
 }
 
 int dcf_eval_range_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, int party, const uint8_t* cwb,
@@ -2795,36 +2870,121 @@ int dcf_eval_range_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, 
   DeviceGuard dg(p->device);
   Lease L(p);
   if (int rc = L.order((hipStream_t)stream)) return rc;
-#ifndef DCF_RANGEMK_WIDE
-#define DCF_RANGEMK_WIDE 1  // A/B knob: 0 sends these shapes key by key through rangemk_fallback, as before
-#endif
-  if (DCF_RANGEMK_WIDE && p->kind == 0 && p->lambda >= 32 && n_bytes <= 16)
-    return rangemk_wide(p, L, n_bytes, num_keys, party, cwb, s0s, A, count, ys);
-  if (p->lambda != 16 || n_bytes > 16)
-    return rangemk_fallback(p, L, n_bytes, num_keys, party, cwb, s0s, A, count, ys);
-  const uint32_t h = rangemk_levels(n_bytes, num_keys, count);
-  const uint64_t per = std::min<uint64_t>(num_keys, rangemk_keys_per_launch(h, count));
-  size_t buf_bytes;
-  const size_t ws = range_ws_bytes(per, std::min<uint64_t>(count, kRangeLaunch), h, &buf_bytes);
-  if (int rc = range_begin(p, L, ws, true)) return rc;
-  phase_mark(p, L, 1);
-  const auto group = p->kind == 0 ? range_group<RangeHirose, RangeKeys> : range_group<RangeMmo, RangeKeys>;
-  if ((count >> h) + 2 <= (kRangeLaunch >> h)) {  // groups of whole keys
-    for (uint64_t k0 = 0; k0 < num_keys; k0 += per) {
-      const uint64_t keys = std::min<uint64_t>(per, num_keys - k0);
-      if (int rc = group(p, L, n_bytes, num_keys, party, cwb, s0s, k0, keys, A.x, count, h, buf_bytes, ys + k0 * count * 16))
-        return rc;
-    }
-  } else {  // one key alone exceeds a launch: the keys one after another, 2^28 outputs at a time
-    for (uint64_t k = 0; k < num_keys; ++k)
-      for (uint64_t o = 0; o < count; o += kRangeLaunch) {
-        const uint64_t n = std::min<uint64_t>(kRangeLaunch, count - o);
-        if (int rc = group(p, L, n_bytes, num_keys, party, cwb, s0s, k, 1, range_add(A.x, o), n, h, buf_bytes,
-                           ys + (k * count + o) * 16))
-          return rc;
-      }
+  return rangemk_run(p, L, n_bytes, num_keys, 0, num_keys, party, cwb, s0s, A, count, ys, true);
+}
+
+// ---- range fold (kernels_range.h; DESIGN.md "Range fold") ----
+
+constexpr uint64_t kFoldPassRows = 1ull << 22;    // outputs per pass of the row-folding path ...
+constexpr uint64_t kFoldPassBytes = 256ull << 20;  // ... and their bytes, whichever is smaller
+
+static uint64_t fold_pass_rows(size_t lam) { return std::max<uint64_t>(1, std::min(kFoldPassRows, kFoldPassBytes / lam)); }
+
+// out[key] ^= XOR_i rows[key * cnt + i] & w[i] for nk keys (k_fold_rows), on st.
+static int fold_rows(const dcf_prg* p, const uint8_t* rows, const uint8_t* w, uint64_t nk, uint64_t cnt, uint8_t* out,
+                     hipStream_t st) {
+  const uint32_t q = (uint32_t)(p->lambda / 16);
+  const uint64_t elems = cnt * q;
+  // enough threads for one 8-element column walk each, at least one per column, a few waves per CU at most
+  const uint64_t gy = std::min<uint64_t>(nk, 65535);
+  const uint64_t want = std::max<uint64_t>((elems + 7) / 8, q);
+  const uint64_t gx = std::max<uint64_t>(1, std::min<uint64_t>((want + 255) / 256, std::max<uint64_t>(1, 8ull * p->cus / gy)));
+  const uint64_t gx_min = ((uint64_t)q + 255) / 256;  // the stride is at least q
+  const uint64_t g = std::max(gx, gx_min);
+  const uint32_t stride = (uint32_t)(g * 256 / q * q);
+  hipLaunchKernelGGL(k_fold_rows, dim3((unsigned)g, (unsigned)gy), dim3(256), 0, st, (const uint4*)rows, (const uint4*)w,
+                     (uint32_t)nk, cnt, q, stride, (uint32_t*)out);
+  HIP_TRY(hipGetLastError());
+  return DCF_OK;
+}
+
+// One key without a folding tail: the range path in passes of fold_pass_rows outputs into the
+// workspace's fold buffer (behind `reserve` bytes of it that the caller uses), each folded into
+// `out` (zeroed by the caller).  zero_blocks: first part of a call.
+static int fold_passes(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
+                       const RangeArg& A, uint64_t count, const uint8_t* w, uint8_t* out, size_t reserve,
+                       bool zero_blocks) {
+  const size_t lam = p->lambda;
+  const uint64_t pass = std::min<uint64_t>(count, fold_pass_rows(lam));
+  uint8_t* ys = L.w->d_fold + reserve;
+  const uint32_t h = range_levels(nb, count);
+  for (uint64_t o = 0; o < count; o += pass) {
+    const uint64_t n = std::min<uint64_t>(pass, count - o);
+    if (int rc = range_launch(p, L, nb, party, cwb, s0, A, o, n, h, ys, zero_blocks && o == 0)) return rc;
+    if (int rc = fold_rows(p, ys, w ? w + o * lam : nullptr, 1, n, out, L.st)) return rc;
   }
-  return range_end(p, L);
+  return DCF_OK;
+}
+
+static int ensure_fold(Workspace* w, size_t bytes, hipStream_t st) { return grow(&w->d_fold, &w->fold_bytes, bytes, st); }
+
+// Is the shape fused — does the range call take the lambda = 16 tree path with h > 0?
+static bool fold_fused(const dcf_prg* p, size_t nb, uint32_t h) { return p->lambda == 16 && nb <= 16 && h > 0; }
+
+int dcf_eval_range_fold_device(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
+                               const uint8_t* x0, uint64_t count, const uint8_t* w, uint8_t* out, void* stream) {
+  if (int rc = check_range_args(p, n_bytes, party, cwb, s0, x0)) return rc;
+  if (n_bytes > 16 + kRangeTopMax) return fail(DCF_ERR_UNSUPPORTED, "range eval: N <= 256");
+  if (!out) return fail(DCF_ERR_ARG, "null buffer");
+  RangeArg A;
+  if (count)
+    if (int rc = range_parse(n_bytes, x0, count, &A)) return rc;
+  const size_t lam = p->lambda;
+  DeviceGuard dg(p->device);
+  Lease L(p);
+  if (int rc = L.order((hipStream_t)stream)) return rc;
+  HIP_TRY(hipMemsetAsync(out, 0, lam, L.st));
+  if (count == 0) return DCF_OK;
+  const uint32_t h = range_levels(n_bytes, count);
+  if (fold_fused(p, n_bytes, h))
+    return range_tree(p, L, n_bytes, party, cwb, s0, A, 0, count, h, out, true, RangeFold{(const uint4*)w});
+  if (int rc = ensure_fold(L.w, std::min<uint64_t>(count, fold_pass_rows(lam)) * lam, L.st)) return rc;
+  return fold_passes(p, L, n_bytes, party, cwb, s0, A, count, w, out, 0, true);
+}
+
+int dcf_eval_range_fold_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, int party, const uint8_t* cwb,
+                                        const uint8_t* s0s, const uint8_t* x0, uint64_t count, const uint8_t* w,
+                                        uint8_t* out, void* stream) {
+  if (int rc = check_range_args(p, n_bytes, party, cwb, s0s, x0)) return rc;
+  if (n_bytes > 16 + kRangeTopMax) return fail(DCF_ERR_UNSUPPORTED, "range eval: N <= 256");
+  if (num_keys == 0) return DCF_OK;
+  if (!out) return fail(DCF_ERR_ARG, "null buffer");
+  RangeArg A;
+  if (count)
+    if (int rc = range_parse(n_bytes, x0, count, &A)) return rc;
+  const size_t lam = p->lambda, K = num_keys;
+  DeviceGuard dg(p->device);
+  Lease L(p);
+  if (int rc = L.order((hipStream_t)stream)) return rc;
+  HIP_TRY(hipMemsetAsync(out, 0, K * lam, L.st));
+  if (count == 0) return DCF_OK;
+  const uint32_t h = rangemk_levels(n_bytes, K, count);
+  if (fold_fused(p, n_bytes, h))
+    return rangemk_tree(p, L, n_bytes, K, 0, K, party, cwb, s0s, A, count, h, out, true, RangeFold{(const uint4*)w});
+  const uint64_t rows = fold_pass_rows(lam);
+  if (count <= rows) {  // passes of whole keys
+    const uint64_t per = std::min<uint64_t>(K, rows / count);
+    if (int rc = ensure_fold(L.w, per * count * lam, L.st)) return rc;
+    for (uint64_t k0 = 0; k0 < K; k0 += per) {
+      const uint64_t nk = std::min<uint64_t>(per, K - k0);
+      if (int rc = rangemk_run(p, L, n_bytes, K, k0, nk, party, cwb, s0s, A, count, L.w->d_fold, k0 == 0)) return rc;
+      if (int rc = fold_rows(p, L.w->d_fold, w, nk, count, out + k0 * lam, L.st)) return rc;
+    }
+    return DCF_OK;
+  }
+  // a key is more than a pass: key by key, each gathered into the single-key layout ahead of the pass
+  const size_t kb = align256(dcf_cwb_bytes(n_bytes, lam, 1)), reserve = kb + align256(lam);
+  if (int rc = ensure_fold(L.w, reserve + rows * lam, L.st)) return rc;
+  uint8_t* dk = L.w->d_fold;
+  HIP_TRY(hipMemsetAsync(dk, 0, reserve, L.st));
+  const uint8_t* np1 = cwb + dcf_cwb_np1_offset(n_bytes, lam, K);
+  for (uint64_t k = 0; k < K; ++k) {
+    hipLaunchKernelGGL(k_rangemk_gather, dim3(8), dim3(256), 0, L.st, cwb, np1, s0s, (uint64_t)K, k,
+                       (uint32_t)(8 * n_bytes), (uint32_t)lam, (uint32_t)dcf_cwb_np1_offset(n_bytes, lam, 1), dk, dk + kb);
+    HIP_TRY(hipGetLastError());
+    if (int rc = fold_passes(p, L, n_bytes, party, dk, dk + kb, A, count, w, out + k * lam, reserve, k == 0)) return rc;
+  }
+  return DCF_OK;
 }
 
 int dcf_gen(dcf_prg* p, size_t n_bytes, const uint8_t* alpha, const uint8_t* beta, const uint8_t* s0_0,

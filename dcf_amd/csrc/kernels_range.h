@@ -20,6 +20,9 @@
 //                     leaf's output index is its distance from x0 and leaves outside the range are
 //                     not stored.
 // Each is a template on the key policy, RangeOneKey or RangeKeys, and is instantiated for both.
+// k_range_tail16 is also a template on the output policy: RangeStore writes every leaf inside the
+// range, RangeFold XORs the leaves, each masked by its row of a public table, into one LAMBDA-byte
+// value per key and stores nothing per leaf (DESIGN.md "Range fold").
 // k_range_level16 and k_range_tail16 are also templates on the PRG policy: RangeHirose here,
 // RangeMmo in kernels_range_mmo.h, which has the MMO PRG's own root walk (k_range_roots16_mmo)
 // as well.  kernels_range_wide.h has the three stages over the Hirose PRG's head state at
@@ -28,6 +31,8 @@
 //                     LAMBDA >= 32 and for N > 16, which have no tree-sharing path (the existing
 //                     eval runs on them).
 //   k_rangemk_gather  key k of a K-key block as a single-key block (the same slow path, key by key).
+//   k_fold_rows       the fold of rows that a range call has written: the shapes without a folding
+//                     tail (h = 0, LAMBDA >= 32, N > 16).
 // The pointers the kernels get are already advanced to the first key of the launch group; K stays
 // the row stride.  All node, key and output indices of a tree launch are 32-bit (the host keeps
 // keys * (nroots << h) <= 2^28).
@@ -222,6 +227,71 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_level16(
   if ((threadIdx.x & 63u) == 0 && nlive) atomicAdd(blocks, PRG::kBlocks * nlive);
 }
 
+// Output policies of the tail kernel: what becomes of leaf o (its distance from x0) of a key.
+//   RangeStore  y goes to row o of the key's outputs.
+//   RangeFold   y & w[o] is XORed into four accumulator words of the lane (w: the table of the
+//               launch group, one row per output, shared by all keys; null: no mask).  The words
+//               of a wave are combined without LDS (the workgroup's LDS is the tables) and XORed
+//               into the key's row of `out` with one 4-word atomic update per wave (one key) or
+//               per run of equal keys in the wave (per-lane keys).  The host zeroes `out` on the
+//               stream once per call; XOR is associative and commutative, so the result is exact
+//               whatever the order of the updates.
+//   at(o)       the policy of the launch group that starts at output o of the call.
+struct RangeStore {
+  static constexpr bool kFold = false;
+  RangeStore at(uint64_t) const { return {}; }
+};
+struct RangeFold {
+  static constexpr bool kFold = true;
+  const uint4* w;
+  RangeFold at(uint64_t o) const { return {w ? w + o : nullptr}; }
+  __device__ __forceinline__ uint4 mask(uint32_t o) const { return w ? w[o] : make_uint4(~0u, ~0u, ~0u, ~0u); }
+};
+
+// acc ^= y & m, y = v ^ s ^ t * cw_np1 (nt = 0 - t).
+__device__ __forceinline__ void range_fold_leaf(uint32_t (&acc)[4], const uint32_t (&v)[4], const uint32_t (&s)[4],
+                                                const uint32_t nt, const uint4 np, const uint4 m) {
+  acc[0] ^= (v[0] ^ s[0] ^ (nt & np.x)) & m.x;
+  acc[1] ^= (v[1] ^ s[1] ^ (nt & np.y)) & m.y;
+  acc[2] ^= (v[2] ^ s[2] ^ (nt & np.z)) & m.z;
+  acc[3] ^= (v[3] ^ s[3] ^ (nt & np.w)) & m.w;
+}
+
+// One key: the XOR of the wave's 64 accumulators (butterfly) into out[0..3], by lane 0.
+__device__ __forceinline__ void range_fold_wave(uint32_t (&acc)[4], uint32_t* __restrict__ out) {
+#pragma unroll
+  for (uint32_t d = 32; d; d >>= 1)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] ^= __shfl_xor(acc[e], d);
+  if ((threadIdx.x & 63u) == 0 && (acc[0] | acc[1] | acc[2] | acc[3]))
+#pragma unroll
+    for (int e = 0; e < 4; ++e) atomicXor(out + e, acc[e]);
+}
+
+// Per-lane keys, non-decreasing over the lanes of the wave (node j has key j / per): an inclusive
+// segmented XOR scan over the runs of equal key (lane l takes lane l - d while that lane has l's
+// key; the keys are ordered, so then every lane between has it too), after which the last lane of
+// each run holds the run's XOR and updates out[4 key ..].  Clears acc.
+__device__ __forceinline__ void range_fold_keys(uint32_t (&acc)[4], const uint32_t key, uint32_t* __restrict__ out) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    const uint32_t ok = __shfl_up(key, d);
+    uint32_t o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = __shfl_up(acc[e], d);
+    if (lane >= d && ok == key)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] ^= o[e];
+  }
+  const uint32_t nk = __shfl_down(key, 1u);
+  if ((lane == 63u || nk != key) && (acc[0] | acc[1] | acc[2] | acc[3]))
+#pragma unroll
+    for (int e = 0; e < 4; ++e) atomicXor(out + 4ull * key + e, acc[e]);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc[e] = 0u;
+}
+
 // Tail: k_fd_dfs16's register depth-first expansion of the last H levels from the rows of level
 // lev0 = 8N - H, one lane per node, waves claiming units of nodes from ctr[0] (the stack logic is
 // written out here as there: a function template shared by the two compiled to 3 % more VALU work
@@ -233,14 +303,16 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_level16(
 // PACKED (per-lane correction words, and the MMO PRG always): the node and the stack slots stay in
 // the rows' form, 8 words with t in bit 24 of word 3, the bit s has cleared; the words take the
 // registers that a separate t (9-word nodes) has otherwise.
+// OUT: RangeStore as above; RangeFold: ys is the launch group's first row of `out` (16 bytes per
+// key), the leaves below count are folded and nothing else is written.
 // blocks: the call's AES block count, PRG::kBlocks (2^H - 1) per node — clipped leaves included.
-template <int H, class PRG, class KP>
+template <int H, class PRG, class KP, class OUT>
 __global__ __launch_bounds__(kBlock, 1) void k_range_tail16(
     const uint32_t* __restrict__ tab, const typename PRG::Arg rk, const uint4* __restrict__ cw_s,
     const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const uint4* __restrict__ cw_np1,
     const KP kp, const uint32_t lev0, const uint32_t nnodes, const uint4* __restrict__ rows, const uint32_t skip,
     const uint32_t count, uint4* __restrict__ ys, uint32_t* __restrict__ ctr,
-    unsigned long long* __restrict__ blocks) {
+    unsigned long long* __restrict__ blocks, const OUT op) {
   static_assert(H >= 2 && H <= 4, "register depth-first tail of 2..4 levels");
   constexpr bool PACKED = PRG::kPacked || KP::kPerLane;
   __shared__ uint32_t lds[kLdsWords];
@@ -250,6 +322,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_tail16(
   const uint4 np0 = KP::kPerLane ? make_uint4(0u, 0u, 0u, 0u) : cw_np1[0];
   const uint32_t unit = fd_unit(nnodes);
   uint32_t nlive = 0;  // nodes this wave expanded: one atomic per wave, after its last unit
+  [[maybe_unused]] uint32_t acc[4] = {0u, 0u, 0u, 0u};  // RangeFold: the lane's masked leaves
   for (uint64_t base = next_unit_base_n(ctr, ~0ull, unit); base < nnodes;
        base = next_unit_base_n(ctr, base, unit)) {
     const uint32_t j = (uint32_t)base + (threadIdx.x & 63u);
@@ -293,13 +366,18 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_tail16(
           const uint32_t ol = o0 + 2u * i, orr = ol + 1u;
           const uint32_t ml = 0u - tl, mr = 0u - tr;
           const uint4 np = KP::kPerLane ? cw_np1[key] : np0;
-          uint4* const yk = ys + (uint64_t)key * count;
-          if (ol < count)
-            yk[ol] = make_uint4(vl[0] ^ sl[0] ^ (ml & np.x), vl[1] ^ sl[1] ^ (ml & np.y),
-                                vl[2] ^ sl[2] ^ (ml & np.z), vl[3] ^ sl[3] ^ (ml & np.w));
-          if (orr < count)
-            yk[orr] = make_uint4(vr[0] ^ sr[0] ^ (mr & np.x), vr[1] ^ sr[1] ^ (mr & np.y),
-                                 vr[2] ^ sr[2] ^ (mr & np.z), vr[3] ^ sr[3] ^ (mr & np.w));
+          if constexpr (OUT::kFold) {
+            if (ol < count) range_fold_leaf(acc, vl, sl, ml, np, op.mask(ol));
+            if (orr < count) range_fold_leaf(acc, vr, sr, mr, np, op.mask(orr));
+          } else {
+            uint4* const yk = ys + (uint64_t)key * count;
+            if (ol < count)
+              yk[ol] = make_uint4(vl[0] ^ sl[0] ^ (ml & np.x), vl[1] ^ sl[1] ^ (ml & np.y),
+                                  vl[2] ^ sl[2] ^ (ml & np.z), vl[3] ^ sl[3] ^ (ml & np.w));
+            if (orr < count)
+              yk[orr] = make_uint4(vr[0] ^ sr[0] ^ (mr & np.x), vr[1] ^ sr[1] ^ (mr & np.y),
+                                   vr[2] ^ sr[2] ^ (mr & np.z), vr[3] ^ sr[3] ^ (mr & np.w));
+          }
           break;
         }
 #pragma unroll
@@ -320,7 +398,10 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_tail16(
         if constexpr (!PACKED) n[8] = tl;
       }
     }
+    // idle lanes have the last node's key and folded nothing
+    if constexpr (OUT::kFold && KP::kPerLane) range_fold_keys(acc, key, reinterpret_cast<uint32_t*>(ys));
   }
+  if constexpr (OUT::kFold && !KP::kPerLane) range_fold_wave(acc, reinterpret_cast<uint32_t*>(ys));
   if ((threadIdx.x & 63u) == 0 && nlive) atomicAdd(blocks, PRG::kBlocks * ((1u << H) - 1u) * nlive);
 }
 
@@ -361,6 +442,44 @@ __global__ void k_rangemk_gather(const uint8_t* __restrict__ cwb, const uint8_t*
     } else {
       const uint32_t b = i - (2u * rows + nlev + lam);
       s0_out[b] = s0s[key * lam + b];
+    }
+  }
+}
+
+// The fold of rows a range call has written (the shapes without a folding tail): for each of nk
+// keys, out[key] ^= XOR over i < count of rows[key * count + i] & w[i], on rows of q uint4s
+// (LAMBDA = 16 q).  A key's rows and the table are both count * q uint4s in the same order, so
+// thread g of the S = stride threads of a grid row takes elements g, g + S, ... of both; S is a
+// multiple of q, so they all lie in column g % q (the host keeps S >= q).  q a power of two up to
+// 64: a workgroup starts at a multiple of 64, so lanes l and l ^ d share a column for d >= q, and
+// the wave's partial sums meet in its lanes below q (the butterfly of range_fold_wave, stopped at
+// q) before the atomic update; any other q: every thread updates `out` itself.  w null: no mask.
+// `out` has been zeroed by the call.  blockIdx.y strides over the keys.
+__global__ __launch_bounds__(256) void k_fold_rows(const uint4* __restrict__ rows, const uint4* __restrict__ w,
+                                                   const uint32_t nk, const uint64_t count, const uint32_t q,
+                                                   const uint32_t stride, uint32_t* __restrict__ out) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t n = count * q;
+  const bool pow2 = q <= 64u && (q & (q - 1u)) == 0u;
+  for (uint32_t key = blockIdx.y; key < nk; key += gridDim.y) {
+    const uint4* r = rows + (uint64_t)key * n;
+    uint32_t acc[4] = {0u, 0u, 0u, 0u};
+    if (g < stride)
+      for (uint64_t e = g; e < n; e += stride) {
+        const uint4 y = r[e], m = w ? w[e] : make_uint4(~0u, ~0u, ~0u, ~0u);
+        acc[0] ^= y.x & m.x;
+        acc[1] ^= y.y & m.y;
+        acc[2] ^= y.z & m.z;
+        acc[3] ^= y.w & m.w;
+      }
+    if (pow2)
+      for (uint32_t d = 32; d >= q; d >>= 1)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] ^= __shfl_xor(acc[e], d);
+    if ((!pow2 || (threadIdx.x & 63u) < q) && (acc[0] | acc[1] | acc[2] | acc[3])) {
+      uint32_t* o = out + 4ull * ((uint64_t)key * q + g % q);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) atomicXor(o + e, acc[e]);
     }
   }
 }

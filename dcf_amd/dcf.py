@@ -490,6 +490,52 @@ class DcfImpl:
                                                          py, _stream(dev)))
         return ys
 
+    # ---- range fold: XOR over the range of the outputs, each masked by its row of a public table ----
+    def eval_range_fold_device(self, b: bool, cwb, s0, x0, count: int, w=None, out=None):
+        """XOR over i in [0, count) of `Dcf::eval(b, k, x0 + i) & w[i]` as a (LAMBDA,) device tensor
+        (dcf_eval_range_fold_device).  w: (count, LAMBDA) uint8 device tensor, or None for no mask.
+        `out` is overwritten.  The two parties' values XOR to the XOR of beta & w[i] over the i
+        with x0 + i < alpha (LtBeta).  LAMBDA = 16, N <= 16, count >= 2^12: the tail of
+        eval_range_device's tree folds in registers, so no (count, LAMBDA) buffer exists; other
+        shapes fold eval_range_device's rows pass by pass (include/dcf_hip.h)."""
+        import torch
+        lam, nb, dev = self.lam, self.n_bytes, self.prg.device
+        xb = self._x0(x0)
+        count = int(count)
+        if count < 0:
+            raise DcfError(-1, "count must not be negative")
+        pk = _dev(cwb, "cwb", dev, numel=cwb_bytes(nb, lam, 1))
+        ps = _dev(s0, "s0", dev, numel=lam)
+        pw = None if w is None else _dev(w, "w", dev, numel=count * lam)
+        if out is None:
+            out = torch.empty((lam,), dtype=torch.uint8, device=cwb.device)
+        po = _dev(out, "out", dev, numel=lam)
+        check(_lib.load().dcf_eval_range_fold_device(self.prg.handle, nb, int(bool(b)), pk, ps, _ptr(xb), count, pw, po,
+                                                     _stream(dev)))
+        return out
+
+    def eval_range_fold_multikey_device(self, b: bool, cwb, s0s, x0, count: int, w=None, out=None):
+        """K keys over one range and one table: row k of the (K, LAMBDA) result is the fold of key k
+        (dcf_eval_range_fold_multikey_device).  cwb: the K-key block of gen_batch_device, s0s
+        (K, LAMBDA), w (count, LAMBDA) or None.  Fused with eval_range_multikey_device's tree where
+        range_multikey_subtree_levels(K, count) > 0 at LAMBDA = 16, N <= 16."""
+        import torch
+        lam, nb, dev = self.lam, self.n_bytes, self.prg.device
+        xb = self._x0(x0)
+        count = int(count)
+        if count < 0:
+            raise DcfError(-1, "count must not be negative")
+        K = s0s.shape[0] if s0s.dim() == 2 else -1
+        ps = _dev(s0s, "s0s", dev, shape=(K, lam))
+        pk = _dev(cwb, "cwb", dev, numel=cwb_bytes(nb, lam, K))
+        pw = None if w is None else _dev(w, "w", dev, numel=count * lam)
+        if out is None:
+            out = torch.empty((K, lam), dtype=torch.uint8, device=s0s.device)
+        po = _dev(out, "out", dev, numel=K * lam)
+        check(_lib.load().dcf_eval_range_fold_multikey_device(self.prg.handle, nb, K, int(bool(b)), pk, ps, _ptr(xb),
+                                                              count, pw, po, _stream(dev)))
+        return out
+
     def eval_range(self, b: bool, k: Share, x0, count: int, ys=None):
         """Host buffers (dcf_eval_range): ys is a (count, LAMBDA) uint8 numpy array, overwritten in
         place when given.  Returns ys.  The chunks run eval_range_device's path for the shape (tree

@@ -255,6 +255,24 @@ class DcfImpl final : public Dcf<N, LAMBDA> {
                                          stream));
   }
 
+  // Range fold (dcf_eval_range_fold_device): out (LAMBDA bytes, overwritten) = XOR over i in
+  // [0, count) of Dcf::eval(b, k, x0 + i) & w[i].  w: count * LAMBDA bytes on the device, row i
+  // masks point x0 + i, or nullptr for no mask.  Fused with the tree's tail where eval_range_device
+  // takes the LAMBDA = 16 tree path (count >= 2^12): no count * LAMBDA buffer exists.
+  void eval_range_fold_device(bool b, const uint8_t* cwb, const uint8_t* s0, const std::array<uint8_t, N>& x0,
+                              uint64_t count, const uint8_t* w, uint8_t* out, void* stream = nullptr) const {
+    check(dcf_eval_range_fold_device(prg_.handle(), N, b ? 1 : 0, cwb, s0, x0.data(), count, w, out, stream));
+  }
+
+  // The same for num_keys keys over one range and one table (dcf_eval_range_fold_multikey_device):
+  // row k of out (num_keys * LAMBDA bytes, overwritten) is the fold of key k.
+  void eval_range_fold_multikey_device(bool b, size_t num_keys, const uint8_t* cwb, const uint8_t* s0s,
+                                       const std::array<uint8_t, N>& x0, uint64_t count, const uint8_t* w,
+                                       uint8_t* out, void* stream = nullptr) const {
+    check(dcf_eval_range_fold_multikey_device(prg_.handle(), N, num_keys, b ? 1 : 0, cwb, s0s, x0.data(), count, w,
+                                              out, stream));
+  }
+
   // Block height and whole keys per launch group of eval_range_multikey_device.
   static int range_multikey_subtree_levels(size_t num_keys, uint64_t count) {
     return dcf_eval_range_multikey_subtree_levels(N, num_keys, count);

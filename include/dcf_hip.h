@@ -493,6 +493,62 @@ int dcf_eval_range_wide_multikey_subtree_levels(size_t n_bytes, size_t num_keys,
  * (n_bytes == 0, n_bytes > 16, num_keys == 0, lambda < 32) and for count == 0. */
 size_t dcf_eval_range_wide_keys_per_launch(size_t n_bytes, size_t lambda, size_t num_keys, uint64_t count);
 
+/* Range fold: the XOR of a key's range outputs, each masked by its row of a public table,
+ *   out = XOR over i in [0, count) of ( Dcf::eval(party, k, x0 + i) AND w[i] ),
+ * one lambda-byte value instead of the count * lambda bytes of dcf_eval_range_device.  The two
+ * parties' values XOR to the XOR of beta & w[i] over the i with x0 + i < alpha (LtBeta; > alpha for
+ * GtBeta): the prefix-XOR of the table up to the secret alpha when beta is all-ones.  cwb, s0, w
+ * (count * lambda bytes, row i masks point x0 + i; NULL: no mask, the plain XOR of the outputs) and
+ * out (lambda bytes, OVERWRITTEN, not accumulated into) are device pointers, 16-byte aligned; x0 is a
+ * HOST pointer to n_bytes big-endian bytes, read before the call returns.  Asynchronous on
+ * `stream`.
+ *   Fused — lambda = 16, N <= 16, either PRG, count >= 2^12 (h = dcf_eval_range_subtree_levels
+ *   > 0): dcf_eval_range_device's tree path with the same blocks, heights, launch groups of 2^28
+ *   outputs, workspace (4 B per output of a group), root and level kernels; only the tail kernel
+ *   differs: it loads w[i] for each leaf inside the range, XORs the masked leaf into four words of
+ *   the lane, combines the lanes of a wave by shuffles and updates `out` with one 4-word atomic XOR
+ *   per wave.  `out` is zeroed on the stream once per call and all groups fold into it; no buffer
+ *   of count * lambda bytes exists.  dcf_prg_last_eval_blocks then reports exactly what
+ *   dcf_eval_range_device reports for the shape: per group
+ *     nroots (2 (8N - h) + 2 (2^h - 1)) AES-256 blocks (Hirose),
+ *     nroots (2 (8N - h) + 4 (2^h - 1)) AES-128 blocks (MMO),
+ *     nroots = (((x mod 2^h) + n - 1) >> h) + 1 for a group of n outputs from x.
+ *   Otherwise (count < 2^12, lambda >= 32, N > 16): dcf_eval_range_device's path for the shape
+ *   runs in passes of min(2^22, 256 MiB / lambda) outputs into a buffer of the workspace (at most
+ *   256 MiB, kept with the workspace, counted by dcf_prg_device_bytes) and k_fold_rows XORs each
+ *   pass's masked rows into `out`.  No stream wait, except for the MMO PRG at lambda >= 32 and for
+ *   N > 16, where the range path itself waits for the stream in every pass.
+ * Errors, nothing launched: those of dcf_eval_range_device (x0 + count > 2^(8N), bad party, null
+ * prg / cwb / s0 / x0 -> DCF_ERR_ARG; n_bytes == 0 -> DCF_ERR_N; N > 256 -> DCF_ERR_UNSUPPORTED);
+ * null out -> DCF_ERR_ARG.  count == 0 -> DCF_OK, out = lambda zero bytes (the empty XOR). */
+int dcf_eval_range_fold_device(dcf_prg* prg, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
+                               const uint8_t* x0, uint64_t count, const uint8_t* w, uint8_t* out, void* stream);
+
+/* The same for the K keys of a K-key block (as dcf_eval_range_multikey_device takes it) over one
+ * range and one table: out[k] = XOR_i ( Dcf::eval(party, key k, x0 + i) AND w[i] ), K * lambda
+ * bytes, overwritten.  All keys share w; a per-key rotation of the table is not offered.
+ *   Fused — lambda = 16, N <= 16, either PRG, h = dcf_eval_range_multikey_subtree_levels > 0:
+ *   dcf_eval_range_multikey_device's tree path, same launch groups of
+ *   dcf_eval_range_keys_per_launch whole keys and same workspace, with the folding tail.  The lanes
+ *   of a wave differ in their key (node j of a level with `per` nodes per key has key j / per, so
+ *   the keys are non-decreasing over the lanes): after its 16 leaves each lane enters a segmented
+ *   XOR scan over the runs of equal key, and the last lane of each run updates out[key] — one
+ *   4-word atomic XOR per (wave, key).  When one key alone exceeds 2^28 outputs, its groups fold
+ *   into the same row; the table offset across groups is 64-bit.  Needs K * lambda bytes of output
+ *   and the range call's workspace, nothing else.  dcf_prg_last_eval_blocks reports what
+ *   dcf_eval_range_multikey_device reports: keys * nroots (2 (8N - h) + B (2^h - 1)) per group,
+ *   B = 2 (Hirose, AES-256) or 4 (MMO, AES-128).
+ *   Otherwise (h = 0, lambda >= 32, N > 16): dcf_eval_range_multikey_device's path for the shape
+ *   over passes of whole keys — as many as fit min(2^22, 256 MiB / lambda) outputs — into the
+ *   workspace's fold buffer, each folded by k_fold_rows; a key of more outputs than a pass is
+ *   gathered into the single-key layout and run as dcf_eval_range_fold_device's passes.  No stream
+ *   wait, except for the MMO PRG at lambda >= 32 and for N > 16 (as the range call).
+ * Errors as above (null s0s -> DCF_ERR_ARG).  num_keys == 0 -> DCF_OK, nothing written;
+ * count == 0 -> DCF_OK, out = K * lambda zero bytes. */
+int dcf_eval_range_fold_multikey_device(dcf_prg* prg, size_t n_bytes, size_t num_keys, int party, const uint8_t* cwb,
+                                        const uint8_t* s0s, const uint8_t* x0, uint64_t count, const uint8_t* w,
+                                        uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

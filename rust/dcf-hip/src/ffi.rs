@@ -86,4 +86,10 @@ extern "C" {
     pub fn dcf_eval_range_keys_per_launch(n_bytes: usize, num_keys: usize, count: u64) -> usize;
     pub fn dcf_eval_range_wide_multikey_subtree_levels(n_bytes: usize, num_keys: usize, count: u64) -> c_int;
     pub fn dcf_eval_range_wide_keys_per_launch(n_bytes: usize, lambda: usize, num_keys: usize, count: u64) -> usize;
+    pub fn dcf_eval_range_fold_device(prg: *mut DcfPrg, n_bytes: usize, party: c_int, cwb: *const u8, s0: *const u8,
+                                      x0: *const u8, count: u64, w: *const u8, out: *mut u8, stream: *mut c_void)
+                                      -> c_int;
+    pub fn dcf_eval_range_fold_multikey_device(prg: *mut DcfPrg, n_bytes: usize, num_keys: usize, party: c_int,
+                                               cwb: *const u8, s0s: *const u8, x0: *const u8, count: u64,
+                                               w: *const u8, out: *mut u8, stream: *mut c_void) -> c_int;
 }

@@ -177,6 +177,31 @@ impl<const N: usize, const LAMBDA: usize> DcfHip<N, LAMBDA> {
                                                   stream))
     }
 
+    /// Range fold, device buffers (`dcf_eval_range_fold_device`): `out` (`LAMBDA` bytes, overwritten)
+    /// becomes the XOR over `i < count` of `Dcf::eval(b, k, x0 + i) & w[i]`.  `w` is `count * LAMBDA`
+    /// bytes, or null for no mask; asynchronous on `stream`, `x0` is read before the call returns.
+    ///
+    /// # Safety
+    /// `cwb`, `s0`, `w` (unless null) and `out` must be device buffers of those sizes on the prg's
+    /// device, valid until the work queued on `stream` has finished.
+    pub unsafe fn eval_range_fold_device(&self, b: bool, cwb: *const u8, s0: *const u8, x0: &[u8; N], count: u64,
+                                         w: *const u8, out: *mut u8, stream: *mut c_void) -> Result<(), DcfHipError> {
+        check(ffi::dcf_eval_range_fold_device(self.prg, N, b as c_int, cwb, s0, x0.as_ptr(), count, w, out, stream))
+    }
+
+    /// The same for `num_keys` keys over one range and one table
+    /// (`dcf_eval_range_fold_multikey_device`): row `k` of `out` (`num_keys * LAMBDA` bytes) is the
+    /// fold of key `k`.
+    ///
+    /// # Safety
+    /// As `eval_range_fold_device`, with `cwb` the K-key block and `s0s` `num_keys * LAMBDA` bytes.
+    pub unsafe fn eval_range_fold_multikey_device(&self, b: bool, num_keys: usize, cwb: *const u8, s0s: *const u8,
+                                                  x0: &[u8; N], count: u64, w: *const u8, out: *mut u8,
+                                                  stream: *mut c_void) -> Result<(), DcfHipError> {
+        check(ffi::dcf_eval_range_fold_multikey_device(self.prg, N, num_keys, b as c_int, cwb, s0s, x0.as_ptr(), count,
+                                                       w, out, stream))
+    }
+
     /// Height of the aligned blocks `eval_range_multikey_device` expands (`dcf_eval_range_multikey_subtree_levels`).
     pub fn range_multikey_subtree_levels(num_keys: usize, count: u64) -> i32 {
         unsafe { ffi::dcf_eval_range_multikey_subtree_levels(N, num_keys, count) }

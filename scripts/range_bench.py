@@ -7,7 +7,13 @@ or --lam (the Hirose PRG at LAMBDA >= 32 takes 18 keys; blocks are then the AES-
   (c) N = 4 over the whole domain next to eval_full_domain_device, in the same run;
   (d) the executed blocks/s of (a) as a fraction of the T-table LDS bound: 256 CUs x 32 lookups/clk
       x 2.4 GHz over the lookups of a block, 224 for AES-256 (87.77e9 blocks/s, Hirose) and 160 for
-      AES-128 (122.88e9, MMO).
+      AES-128 (122.88e9, MMO);
+  (e) K keys over one small range (--multikey LOG2_K,COUNT, default 2^20 keys x 256 points at N = 1)
+      through eval_range_multikey_device.
+
+--fold times the range fold instead (eval_range_fold_device for (a), eval_range_fold_multikey_device
+for (e), under a random table of count rows; "fold_checksum" is the folded value) and leaves (b)
+and (c) out, so a --fold run and a plain run on the same shapes stand side by side.
 
 Every figure is the median of REPS >= 10 repetitions timed one by one with HIP events after
 WARMUP untimed ones; min and max are kept beside it.  Prints one JSON document and writes it to
@@ -15,6 +21,7 @@ WARMUP untimed ones; min and max are kept beside it.  Prints one JSON document a
 
   python scripts/range_bench.py [--prg hirose|mmo] [--lam 16] [--log2-counts 16,20,24,28] [--out FILE]
                                 [--reps 10] [--warmup 3] [--skip-full-domain] [--skip-pointwise]
+                                [--fold] [--multikey 20,256 | --skip-multikey]
 
 --skip-pointwise leaves (b) out (at LAMBDA = 16384 and 2^22 points its outputs are a second 64 GiB);
 every range row carries a checksum of its outputs, so two libraries can be compared run to run.
@@ -82,9 +89,15 @@ def main():
     ap.add_argument("--skip-pointwise", action="store_true")
     ap.add_argument("--lam", type=int, default=16)
     ap.add_argument("--log2-counts", default="16,20,24,28")
+    ap.add_argument("--fold", action="store_true")
+    ap.add_argument("--multikey", default="20,256")
+    ap.add_argument("--skip-multikey", action="store_true")
     a = ap.parse_args()
+    if a.fold:
+        a.skip_full_domain = a.skip_pointwise = True
     assert a.reps >= 10, "median of at least 10 repetitions"
-    a.out = a.out or os.path.join("profiles", "range_bench.json" if a.prg == "hirose" else f"range_bench_{a.prg}.json")
+    stem = "range_fold_bench" if a.fold else "range_bench"
+    a.out = a.out or os.path.join("profiles", f"{stem}.json" if a.prg == "hirose" else f"{stem}_{a.prg}.json")
     LDS_BOUND_BLOCKS_PER_S = LDS_LOOKUPS_PER_S / LDS_PER_BLOCK[a.prg]
     lam = a.lam
     rng = np.random.default_rng(0x7A)
@@ -92,7 +105,7 @@ def main():
         prg = dcf_amd.Aes128MatyasMeyerOseasPrg([rng.bytes(16) for _ in range(4 * lam // 16)], lam)
     else:
         prg = dcf_amd.Aes256HirosePrg([rng.bytes(32) for _ in range(2 if lam == 16 else 18)], lam)
-    res = {"device": torch.cuda.get_device_name(0), "prg": a.prg, "lambda": lam,
+    res = {"device": torch.cuda.get_device_name(0), "prg": a.prg, "lambda": lam, "fold": a.fold,
            "library": dcf_amd.load().dcf_version().decode(),
            "lds_bound_blocks_per_s": LDS_BOUND_BLOCKS_PER_S, "ranges": []}
 
@@ -102,15 +115,22 @@ def main():
     for e in (int(v) for v in a.log2_counts.split(",")):
         count = 1 << e
         cwb, s0 = key(d, nb, lam, rng, x0 + count // 3)
-        ys = torch.empty((count, lam), dtype=torch.uint8, device="cuda")
-        t = timed(lambda: d.eval_range_device(False, cwb, s0, x0, count, ys), a.reps, a.warmup)
+        if a.fold:
+            w = torch.randint(0, 256, (count, lam), dtype=torch.uint8, device="cuda")
+            ys = torch.empty((lam,), dtype=torch.uint8, device="cuda")
+            t = timed(lambda: d.eval_range_fold_device(False, cwb, s0, x0, count, w, ys), a.reps, a.warmup)
+        else:
+            ys = torch.empty((count, lam), dtype=torch.uint8, device="cuda")
+            t = timed(lambda: d.eval_range_device(False, cwb, s0, x0, count, ys), a.reps, a.warmup)
         blocks = prg.last_eval_blocks()
         row = {"n_bytes": nb, "count": count, "subtree_levels": d.range_subtree_levels(count),
                "range": t, "range_outputs_per_s": count / (t["median_ms"] * 1e-3),
                "blocks": blocks, "blocks_per_output": blocks / count,
                "blocks_per_s": blocks / (t["median_ms"] * 1e-3),
                "lds_bound_frac": blocks / (t["median_ms"] * 1e-3) / LDS_BOUND_BLOCKS_PER_S,
-               "ys_checksum": int(ys.view(torch.int64).sum().item())}
+               "fold_checksum" if a.fold else "ys_checksum": int(ys.view(torch.int64).sum().item())}
+        if a.fold:
+            del w
         if not a.skip_pointwise:
             xs = points(x0, count, nb)
             yp = torch.empty((count, lam), dtype=torch.uint8, device="cuda")
@@ -121,6 +141,32 @@ def main():
         res["ranges"].append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
         del ys
+        torch.cuda.empty_cache()
+
+    if not a.skip_multikey:
+        nb = 1
+        lk, count = (int(v) for v in a.multikey.split(","))
+        K = 1 << lk
+        d = dcf_amd.DcfImpl(nb, lam, prg)
+        g = torch.Generator(device="cuda").manual_seed(0x7A)
+        r = lambda *shape: torch.randint(0, 256, shape, dtype=torch.uint8, device="cuda", generator=g)  # noqa: E731
+        s0 = r(K, lam)
+        cwb = d.gen_batch_device(r(K, nb), r(K, lam), s0, r(K, lam), dcf_amd.BoundState.LtBeta)
+        if a.fold:
+            w = r(count, lam)
+            ys = torch.empty((K, lam), dtype=torch.uint8, device="cuda")
+            t = timed(lambda: d.eval_range_fold_multikey_device(False, cwb, s0, 0, count, w, ys), a.reps, a.warmup)
+        else:
+            ys = torch.empty((K, count, lam), dtype=torch.uint8, device="cuda")
+            t = timed(lambda: d.eval_range_multikey_device(False, cwb, s0, 0, count, ys), a.reps, a.warmup)
+        blocks = prg.last_eval_blocks()
+        res["multikey"] = {"n_bytes": nb, "keys": K, "count": count,
+                           "subtree_levels": d.range_multikey_subtree_levels(K, count), "range": t,
+                           "range_outputs_per_s": K * count / (t["median_ms"] * 1e-3), "blocks": blocks,
+                           "blocks_per_output": blocks / (K * count),
+                           "fold_checksum" if a.fold else "ys_checksum": int(ys.view(torch.int64).sum().item())}
+        print(json.dumps(res["multikey"]), file=sys.stderr, flush=True)
+        del ys, cwb
         torch.cuda.empty_cache()
 
     if not a.skip_full_domain:

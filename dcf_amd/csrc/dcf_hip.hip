@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <optional>
 #include <thread>
 #include <string>
 #include <utility>
@@ -279,6 +280,8 @@ uint64_t wide_chunk_points(uint32_t tw) {
 constexpr uint64_t kGenChunk = 4096;          // keys per wide-gen launch (scratch 3*LAMBDA per key)
 constexpr uint32_t kTailPts = 4096;          // points per tail workgroup (one table build each)
 
+size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
 // Grow a workspace buffer to `need` bytes (contents not kept).  The old buffer may still be
 // read by this workspace's earlier work on `st`, so that drains first.
 int grow(uint8_t** buf, size_t* have, size_t need, hipStream_t st) {
@@ -441,6 +444,7 @@ uint32_t wide_prefix_depth(const dcf_prg* p, const Cfg& c, size_t n_bytes, uint6
 // The multi-key shapes eval_wide_batch takes: several keys of few points each (larger keys amortise their own
 // launches: eval_wide per key), Hirose PRG, no forced prefix depth (that runs the per-key passes, a table each).
 constexpr uint64_t kWideBatchPpk = 32768;
+constexpr uint64_t kWideBatchKeys = 4096;  // keys per pass: tail grid rows (keys x <= 8 ranges) <= 32768
 bool wide_batched(const dcf_prg* p, const Cfg& c, uint64_t num_keys, uint64_t ppk) {
   return num_keys > 1 && ppk > 0 && p->kind == 0 && ppk <= kWideBatchPpk && c.prefix_levels <= 0;
 }
@@ -506,6 +510,119 @@ EvalPlan plan_eval(const dcf_prg* p, const Cfg& c, size_t n_bytes, uint64_t num_
   else if (stream && num_keys > 1 && ppk >= (1ull << 31)) pl.unsupported = "multi-key stream eval: 2^31 points per key or more";
   else if (stream) pl.depth = prefix_depth(p, c, n_bytes, num_keys, total);  // (one key only)
   else if ((total + 63) / 64 > 0xFFFFFFFFull) pl.unsupported = "more than 2^32 64-point units";
+  return pl;
+}
+
+// ---- One plan per range call: plan_range() alone tests the range paths' thresholds;
+// range_run and its engines, the fold and the dcf_eval_range_* introspection exports read the plan ----
+constexpr uint64_t kRangeDirectMax = 1ull << 12;    // single-key rule: counts below this walk every point (h = 0)
+constexpr uint64_t kRangeMkDirectMax = 1ull << 12;  // multi-key rule: fewer outputs than this in the whole call: h = 0
+constexpr uint64_t kRangeLaunch = 1ull << 28;  // outputs per launch group of the tree paths (32-bit node and leaf indices)
+constexpr uint32_t kRangeCtrs = 16;            // work counters of a launch group: one per level launch and the tail's last
+#ifndef DCF_RANGEMK_WIDE
+#define DCF_RANGEMK_WIDE 1  // A/B knob: 0 runs K keys at lambda >= 32 one after another under the single-key rule
+#endif
+
+enum class RangeEngine {
+  Tree16,  // lambda = 16, N <= 16, either PRG: range_group (kernels_range.h, kernels_range_mmo.h)
+  Wide,    // Hirose, lambda >= 32, N <= 16: range_wide_group (kernels_range_wide.h)
+  Points,  // everything else: the points are materialised and run through eval
+};
+// The two height rules of include/dcf_hip.h: dcf_eval_range_device, dcf_eval_range and the single-key fold plan
+// under OneKey, the multi-key entry points under MultiKey (count = 5000, one key: h = 8 and h = 10).
+enum class RangeRule { OneKey, MultiKey };
+
+// The one workspace allocation of a Wide launch group of `keys` keys of n outputs each: [t-vectors, 64 B
+// per output (lambda > 32; + 256 B as eval_wide: a tail's clamped t loads run past the last row) |
+// two ping-pong buffers of the 80-byte nodes of the level above the register tail | the roots'
+// t-vector prefixes, 64 B each (lambda > 32) | kRangeCtrs work counters].  The paired-slot tail's
+// per-workgroup counters are a buffer of their own (Workspace::d_tctr), not part of this.
+struct RangeWideWs {
+  size_t tv, buf, pre, total;
+};
+RangeWideWs range_wide_ws(uint64_t n, uint32_t h, size_t lam, uint64_t keys, uint32_t tail) {
+  RangeWideWs r;
+  const uint64_t maxroots = keys * ((n >> h) + 2);
+  n *= keys;
+  r.tv = lam > 32 ? align256(n * kTWords * 4) + 256 : 0;
+  r.buf = h ? align256((maxroots * 80) << (h - tail)) : 0;
+  r.pre = h && lam > 32 ? align256(maxroots * kTWords * 4) : 0;
+  r.total = r.tv + 2 * r.buf + r.pre + kRangeCtrs * sizeof(uint32_t);
+  return r;
+}
+
+// Workspace of a Tree16 launch group: two ping-pong buffers of *buf_bytes each — the rows (32 B) of the
+// level above the tail, for `keys` keys with n <= 2^28 outputs each (4 B per output in all) — then
+// kRangeCtrs work counters.  h = 0 needs none.
+size_t range_ws_bytes(uint64_t keys, uint64_t n, uint32_t h, size_t* buf_bytes) {
+  *buf_bytes = h ? align256((keys * ((n >> h) + 2) * 32) << (h - kFdTail)) : 0;
+  return h ? 2 * *buf_bytes + kRangeCtrs * sizeof(uint32_t) : 0;
+}
+
+struct RangePlan {
+  RangeEngine engine = RangeEngine::Points;
+  uint32_t h = 0;        // height of the aligned blocks (whatever the engine: Points does not read it)
+  // Launch groups hold whole keys, `keys` of them at most, each key's whole count; otherwise (keys = 1)
+  // the keys run one after another, `per` outputs of one key to a group.
+  bool grouped = false;
+  uint64_t keys = 1;
+  uint64_t gkeys = 1;    // keys of a group in this call: min(keys, the keys planned for)
+  uint64_t per = 0;      // kRangeLaunch, or the t-vector buffer's bound on the Wide engine
+  bool per_lane = false;  // the kernels' key policy: RangeKeys / RangeDigKeys, not RangeOneKey
+  uint32_t tail = 0;     // Wide: register depth of the tail
+  bool fused = false;    // a fold of this shape runs in the tree path's tail (Tree16, h > 0)
+  size_t lam = 0;
+  uint64_t count = 0;    // points per key of the call planned
+  // The workspace of a driver call over cnt <= count points of each key (a host chunk and a fold pass
+  // size it for their own points, the height staying the call's).
+  size_t tree_ws(uint64_t cnt, size_t* buf_bytes) const {
+    return range_ws_bytes(gkeys, std::min(cnt, per), h, buf_bytes);
+  }
+  RangeWideWs wide_ws(uint64_t cnt) const { return range_wide_ws(std::min(cnt, per), h, lam, gkeys, tail); }
+};
+
+// `kind`, `lam`: the prg's.  The heights and groups are those of a call of num_keys keys (a pass of an
+// unfused multi-key fold plans on its own keys) of `count` points each.
+RangePlan plan_range(int kind, size_t lam, size_t n_bytes, uint64_t num_keys, uint64_t count, RangeRule rule) {
+  RangePlan pl;
+  pl.lam = lam;
+  pl.count = count;
+  pl.engine = kind == 0 && lam >= 32 && n_bytes <= 16 ? RangeEngine::Wide
+              : lam == 16 && n_bytes <= 16            ? RangeEngine::Tree16
+                                                      : RangeEngine::Points;
+  const bool wide = pl.engine == RangeEngine::Wide;
+  const bool multi = rule == RangeRule::MultiKey && (!wide || DCF_RANGEMK_WIDE);
+  // The height (the rules are documented in include/dcf_hip.h).  One key: 0 below 2^12 points.  K keys:
+  // 2^h <= count / 4 (h >= kFdTail = 4 needs count >= 64), 0 below 2^12 outputs in the whole call; on the
+  // Wide engine the single-key rule from 2^12 points per key, where a key has at least 16 blocks of its own.
+  const uint32_t lg = 63u - (uint32_t)__builtin_clzll(count | 1u);
+  if (!multi || (wide && count >= kRangeDirectMax))
+    pl.h = count < kRangeDirectMax ? 0u : std::min<uint32_t>(kRangeMaxH, std::max<uint32_t>(8u, lg - 8u));
+  else  // K * count < 2^12 <=> K < ceil(2^12 / count)
+    pl.h = count < (4ull << kFdTail) || num_keys < (kRangeMkDirectMax + count - 1) / count
+               ? 0u
+               : std::min<uint32_t>(kRangeMaxH, lg - 2u);
+  pl.h = (uint32_t)std::min<uint64_t>(pl.h, 8 * (uint64_t)n_bytes);
+  // Whole keys per launch group: every key has at most (count >> h) + 2 blocks of 2^h leaves.
+  const uint64_t maxroots = (count >> pl.h) + 2, span = maxroots << pl.h;
+  if (wide) {  // a group's bound is the t-vector buffer's, as eval_wide bounds its passes, and 2^28
+    pl.per = std::min<uint64_t>(wide_chunk_points(t_words((uint32_t)(8 * n_bytes))), kRangeLaunch);
+    pl.grouped = multi && count <= kWideBatchPpk && span <= pl.per;
+    if (pl.grouped) {
+      const uint64_t rpk = std::max<uint64_t>(1, (count + kTailPts - 1) / kTailPts);  // launch_tail's grid rows per key
+      const uint64_t kdig = std::max<uint64_t>(1, (0xFFFFFFFFull / 4u) / (8 * n_bytes));  // as eval_wide_batch
+      pl.keys = std::max<uint64_t>(1, std::min<uint64_t>({pl.per / span, kWideBatchKeys, 8 * kWideBatchKeys / rpk, kdig}));
+    }
+    pl.per_lane = pl.grouped;
+    pl.tail = pl.grouped ? kRangeWideTailKeys : kRangeWideTail;
+  } else {
+    pl.per = kRangeLaunch;
+    pl.grouped = multi && maxroots <= (kRangeLaunch >> pl.h);  // else one key alone is more than a launch
+    if (pl.grouped) pl.keys = std::max<uint64_t>(1, kRangeLaunch / span);
+    pl.per_lane = multi;
+    pl.fused = pl.engine == RangeEngine::Tree16 && pl.h > 0;
+  }
+  pl.gkeys = std::min<uint64_t>(pl.keys, std::max<uint64_t>(num_keys, 1));
   return pl;
 }
 
@@ -977,8 +1094,6 @@ int eval_wide(dcf_prg* p, uint32_t d, Workspace* w, size_t n_bytes, uint64_t K, 
 // point / ppk) and one tail launch whose workgroups build the tables of their own key.  For the
 // shapes of wide_batched() (ppk <= kWideBatchPpk).  No shared prefix; the MMO PRG keeps the
 // per-key path.
-constexpr uint64_t kWideBatchKeys = 4096;  // keys per pass: tail grid rows (keys x <= 8 ranges) <= 32768
-
 int eval_wide_batch(dcf_prg* p, Workspace* w, size_t n_bytes, uint64_t K, uint64_t ppk, int party,
                     const uint8_t* cwb, const uint8_t* s0s, const uint8_t* xs, uint8_t* ys, hipStream_t st) {
   const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * n_bytes);
@@ -1825,8 +1940,6 @@ int dcf_eval_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, size_t
 
 // ---- host-pointer path: per-workspace streams and staging, chunked pipeline ----
 
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // Points per chunk of the host eval pipeline: ~128 MiB of x + y per buffer (C3 shape: 4 Mi
 // points, an 8 ms kernel against ~3 ms of PCIe each way, so the copies hide behind it).
 constexpr size_t kHostChunkBytes = 128ull << 20;
@@ -2261,20 +2374,39 @@ int dcf_eval_full_domain_device(dcf_prg* p, size_t n_bytes, int party, const uin
 
 // ---- contiguous-range eval (kernels_range.h; DESIGN.md "Range eval") ----
 
-constexpr uint64_t kRangeDirectMax = 1ull << 12;  // counts below this walk every point (h = 0)
-constexpr uint64_t kRangeLaunch = 1ull << 28;     // outputs per launch group of the tree path (32-bit node and leaf indices)
-constexpr uint64_t kRangeChunk = 1ull << 22;      // points per pass of the materialising path
+constexpr uint64_t kRangeChunk = 1ull << 22;  // points per pass of the materialising path
 
-// Height of the aligned blocks the tree path uses (the rule is documented in include/dcf_hip.h).
-static uint32_t range_levels(size_t n_bytes, uint64_t count) {
-  if (count < kRangeDirectMax) return 0;
-  const uint32_t lg = 63u - (uint32_t)__builtin_clzll(count);
-  const uint32_t h = std::min<uint32_t>(kRangeMaxH, std::max<uint32_t>(8u, lg - 8u));
-  return (uint32_t)std::min<uint64_t>(h, 8 * (uint64_t)n_bytes);
+// The introspection exports: fields of a plan (the heights and the Tree16 groups do not depend on the
+// PRG; the Wide ones are those of the Hirose PRG at `lambda`, 0 for a shape that engine does not take).
+int dcf_eval_range_subtree_levels(size_t n_bytes, uint64_t count) {
+  return n_bytes ? (int)plan_range(0, 16, n_bytes, 1, count, RangeRule::OneKey).h : 0;
 }
 
-int dcf_eval_range_subtree_levels(size_t n_bytes, uint64_t count) {
-  return n_bytes ? (int)range_levels(n_bytes, count) : 0;
+uint64_t dcf_eval_range_wide_points_per_launch(size_t n_bytes, size_t lambda) {
+  if (!n_bytes) return 0;
+  const RangePlan pl = plan_range(0, lambda, n_bytes, 1, 1, RangeRule::OneKey);
+  return pl.engine == RangeEngine::Wide ? pl.per : 0;
+}
+
+int dcf_eval_range_multikey_subtree_levels(size_t n_bytes, size_t num_keys, uint64_t count) {
+  return n_bytes && num_keys ? (int)plan_range(0, 16, n_bytes, num_keys, count, RangeRule::MultiKey).h : 0;
+}
+
+size_t dcf_eval_range_keys_per_launch(size_t n_bytes, size_t num_keys, uint64_t count) {
+  if (!n_bytes || !count) return 1;
+  return (size_t)plan_range(0, 16, n_bytes, num_keys ? num_keys : 1, count, RangeRule::MultiKey).keys;
+}
+
+int dcf_eval_range_wide_multikey_subtree_levels(size_t n_bytes, size_t num_keys, uint64_t count) {
+  if (!n_bytes || !num_keys || !count) return 0;
+  const RangePlan pl = plan_range(0, 32, n_bytes, num_keys, count, RangeRule::MultiKey);
+  return pl.engine == RangeEngine::Wide ? (int)pl.h : 0;
+}
+
+size_t dcf_eval_range_wide_keys_per_launch(size_t n_bytes, size_t lambda, size_t num_keys, uint64_t count) {
+  if (!n_bytes || !num_keys || !count) return 0;
+  const RangePlan pl = plan_range(0, lambda, n_bytes, num_keys, count, RangeRule::MultiKey);
+  return pl.engine == RangeEngine::Wide ? (size_t)pl.keys : 0;
 }
 
 // x0 as the kernels take it: the low 16 bytes as a 128-bit value and the bytes above them.  Points
@@ -2286,8 +2418,7 @@ struct RangeArg {
   uint64_t first;
 };
 
-static int range_parse(size_t nb, const uint8_t* x0, uint64_t count, RangeArg* A) {
-  if (nb > 16 + kRangeTopMax) return fail(DCF_ERR_UNSUPPORTED, "range eval: N <= 256");
+static int range_parse(size_t nb, const uint8_t* x0, uint64_t count, RangeArg* A) {  // (nb <= 256: RangeCall::check)
   const size_t low = std::min<size_t>(nb, 16), nt = nb - low;
   memset(A, 0, sizeof(*A));
   memcpy(A->top.b, x0, nt);
@@ -2314,15 +2445,32 @@ static int range_parse(size_t nb, const uint8_t* x0, uint64_t count, RangeArg* A
   return DCF_OK;
 }
 
-// What every range entry point checks first (as check_eval_args; ys may be null when there is
-// nothing to write, so the callers look at it after their counts).
-static int check_range_args(dcf_prg* p, size_t n_bytes, int party, const void* cwb, const void* s0s, const void* x0) {
-  if (!p) return fail(DCF_ERR_ARG, "null prg");
-  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
-  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
-  if (!cwb || !s0s || !x0) return fail(DCF_ERR_ARG, "null argument");
-  return DCF_OK;
-}
+// What every range entry point does ahead of its own work, in two steps with the entry's own
+// early-outs between them.  check(): the arguments (as check_eval_args; the prg is not looked into,
+// and ys / out may be null when there is nothing to write, so the callers look at them after their
+// counts).  open(): x0 parsed (count > 0), the prg's device, and a workspace leased and ordered on
+// `stream` — host: on its own compute stream; once L is set the caller ends with host_finish.
+struct RangeCall {
+  RangeArg A;
+  std::optional<DeviceGuard> dg;
+  std::optional<Lease> L;
+  static int check(dcf_prg* p, size_t n_bytes, int party, const void* cwb, const void* s0s, const void* x0) {
+    if (!p) return fail(DCF_ERR_ARG, "null prg");
+    if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
+    if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
+    if (!cwb || !s0s || !x0) return fail(DCF_ERR_ARG, "null argument");
+    if (n_bytes > 16 + kRangeTopMax) return fail(DCF_ERR_UNSUPPORTED, "range eval: N <= 256");
+    return DCF_OK;
+  }
+  int open(dcf_prg* p, size_t n_bytes, const uint8_t* x0, uint64_t count, void* stream, bool host = false) {
+    if (count)
+      if (int rc = range_parse(n_bytes, x0, count, &A)) return rc;
+    dg.emplace(p->device);
+    if (host && !dg->ok) return fail(DCF_ERR_HIP, "hipSetDevice failed");
+    L.emplace(p);
+    return host ? host_lease(*L) : L->order((hipStream_t)stream);
+  }
+};
 
 // Points [off, off + cnt) of the range as N-byte strings at xs.
 static int range_points(const RangeArg& A, size_t nb, uint64_t off, uint64_t cnt, uint8_t* xs, hipStream_t st) {
@@ -2337,16 +2485,6 @@ static int range_points(const RangeArg& A, size_t nb, uint64_t off, uint64_t cnt
     done += n;
   }
   return DCF_OK;
-}
-
-// Workspace of the tree path: two ping-pong buffers of *buf_bytes each — the rows (32 B) of the
-// level above the tail, for `keys` keys with n <= 2^28 outputs each in a launch group (4 B per
-// output in all) — then kRangeCtrs work counters, one per level launch and the tail's last.
-// h = 0 needs none.
-constexpr uint32_t kRangeCtrs = 16;
-static size_t range_ws_bytes(uint64_t keys, uint64_t n, uint32_t h, size_t* buf_bytes) {
-  *buf_bytes = h ? align256((keys * ((n >> h) + 2) * 32) << (h - kFdTail)) : 0;
-  return h ? 2 * *buf_bytes + kRangeCtrs * sizeof(uint32_t) : 0;
 }
 
 // The blocks of 2^h leaves (h >= 1) that cover the n points from xa: the range starts `skip` leaves
@@ -2385,7 +2523,7 @@ static int range_end(dcf_prg* p, Lease& L) {
 // block over the n <= 2^28 points from xa, keys * n <= 2^28; the outputs of key key0 + k go to rows
 // [k * n, (k + 1) * n) of ys (several keys in a group: n is the call's count).  PRG: the prg's PRG
 // policy, RangeHirose or RangeMmo.  KP: the kernels' key policy — RangeOneKey takes key0 = 0,
-// keys = K = 1.  The caller has sized the workspace (range_ws_bytes) and zeroed the block count.
+// keys = K = 1.  The caller has sized the workspace (RangePlan::tree_ws) and zeroed the block count.
 // OUT: the tail's output policy; under RangeFold (h > 0 only) ys is row key0 of the call's `out`,
 // 16 bytes per key, zeroed by the caller, and op holds the group's rows of the table.
 extern "C++" template <class PRG, class KP, class OUT>
@@ -2444,40 +2582,11 @@ static int range_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, con
 
 // ---- range eval over the Hirose PRG at lambda >= 32 (kernels_range_wide.h; DESIGN.md "Range eval, λ ≥ 32") ----
 
-// Outputs per launch group: the t-vector buffer's bound, as eval_wide bounds its passes, and 2^28.
-static uint64_t range_wide_points(size_t nb) {
-  return std::min<uint64_t>(wide_chunk_points(t_words((uint32_t)(8 * nb))), kRangeLaunch);
-}
-
-uint64_t dcf_eval_range_wide_points_per_launch(size_t n_bytes, size_t lambda) {
-  return n_bytes && n_bytes <= 16 && lambda >= 32 ? range_wide_points(n_bytes) : 0;
-}
-
-// The one workspace allocation of a launch group of `keys` keys of n outputs each: [t-vectors, 64 B
-// per output (lambda > 32; + 256 B as eval_wide: a tail's clamped t loads run past the last row) |
-// two ping-pong buffers of the 80-byte nodes of the level above the register tail | the roots'
-// t-vector prefixes, 64 B each (lambda > 32) | kRangeCtrs work counters].  The paired-slot tail's
-// per-workgroup counters are a buffer of their own (Workspace::d_tctr), not part of this.
-struct RangeWideWs {
-  size_t tv, buf, pre, total;
-};
-static RangeWideWs range_wide_ws(uint64_t n, uint32_t h, size_t lam, uint64_t keys = 1,
-                                 uint32_t tail = kRangeWideTail) {
-  RangeWideWs r;
-  const uint64_t maxroots = keys * ((n >> h) + 2);
-  n *= keys;
-  r.tv = lam > 32 ? align256(n * kTWords * 4) + 256 : 0;
-  r.buf = h ? align256((maxroots * 80) << (h - tail)) : 0;
-  r.pre = h && lam > 32 ? align256(maxroots * kTWords * 4) : 0;
-  r.total = r.tv + 2 * r.buf + r.pre + kRangeCtrs * sizeof(uint32_t);
-  return r;
-}
-
 // One launch group: keys [key0, key0 + keys) of a K-key block over the n points from xa; the outputs
 // of key key0 + k go to rows [k * n, (k + 1) * n) of ys (several keys in a group: n is the call's
 // count).  MASK: lambda = 32, the kernels' form without t-vectors.  KP: the kernels' key policy —
 // RangeOneKey takes keys = 1 (any key0 of any K: the key is read in place).  The caller has sized
-// the workspace (range_wide_ws), built the CW digest of the group's keys (dig_t behind its
+// the workspace (RangePlan::wide_ws), built the CW digest of the group's keys (dig_t behind its
 // keys * 8N * 64 bytes) and zeroed the block count.
 extern "C++" template <bool MASK, class KP>
 static int range_wide_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb,
@@ -2536,96 +2645,160 @@ static int range_wide_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party
   return DCF_OK;
 }
 
-// Points [off, off + cnt) of the range into ys by the tree path above, on L.st: no materialised
-// points, no buffer of the call's own, no stream wait.
-static int range_wide_launch(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
-                             const RangeArg& A, uint64_t off, uint64_t cnt, uint32_t h, uint8_t* ys, bool zero_blocks) {
+// ---- the drivers: a plan over keys [key0, key0 + nkeys) of a K-key block, points [off, off + cnt) of
+// the range, one function per engine; a single key is the K = 1 case (DESIGN.md "Range eval") ----
+
+// Tree16, on L.st: launch groups of pl.gkeys whole keys, or the keys one after another in groups of
+// 2^28 outputs.  RangeStore: into ys, the output of point `off` of key key0.  RangeFold (pl.fused):
+// ys is row key0 of the call's `out`, 16 bytes per key, zeroed by the caller — the groups of one key
+// fold into the same row — and op holds the table from point `off`.
+extern "C++" template <class OUT>
+static int range_tree(dcf_prg* p, Lease& L, const RangePlan& pl, size_t nb, size_t K, uint64_t key0, uint64_t nkeys,
+                      int party, const uint8_t* cwb, const uint8_t* s0s, const RangeArg& A, uint64_t off, uint64_t cnt,
+                      uint8_t* ys, bool zero_blocks, const OUT op) {
+  size_t buf_bytes;
+  const size_t ws = pl.tree_ws(cnt, &buf_bytes);
+  if (int rc = range_begin(p, L, ws, zero_blocks)) return rc;
+  phase_mark(p, L, 1);
+  const bool mmo = p->kind != 0;
+  const auto group =
+      pl.per_lane ? (mmo ? range_group<RangeMmo, RangeKeys, OUT> : range_group<RangeHirose, RangeKeys, OUT>)
+                  : (mmo ? range_group<RangeMmo, RangeOneKey, OUT> : range_group<RangeHirose, RangeOneKey, OUT>);
+  const uint64_t row = OUT::kFold ? 1 : cnt;  // rows of ys per key
+  for (uint64_t k0 = key0; k0 < key0 + nkeys; k0 += pl.gkeys) {
+    const uint64_t nk = std::min<uint64_t>(pl.gkeys, key0 + nkeys - k0);
+    for (uint64_t o = 0; o < cnt; o += pl.per) {  // several keys to a group, or h = 0: cnt <= per, one pass
+      const uint64_t n = std::min<uint64_t>(pl.per, cnt - o);
+      if (int rc = group(p, L, nb, K, party, cwb, s0s, k0, nk, range_add(A.x, off + o), n, pl.h, buf_bytes,
+                         ys + ((k0 - key0) * row + (OUT::kFold ? 0 : o)) * 16, op.at(o)))
+        return rc;
+    }
+  }
+  return range_end(p, L);
+}
+
+// Wide, on L.st: launch groups of pl.gkeys whole keys under the per-lane key policy, or the keys one
+// after another through the single-key kernels, each read in place from the K-key block, pl.per
+// outputs to a group.  No materialised points, no gather, no buffer of the call's own, no stream wait.
+static int range_wide(dcf_prg* p, Lease& L, const RangePlan& pl, size_t nb, size_t K, uint64_t key0, uint64_t nkeys,
+                      int party, const uint8_t* cwb, const uint8_t* s0s, const RangeArg& A, uint64_t off, uint64_t cnt,
+                      uint8_t* ys, bool zero_blocks) {
   hipStream_t st = L.st;
   Workspace* w = L.w;
   const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * nb);
-  const uint64_t per = range_wide_points(nb);
-  const RangeWideWs ws = range_wide_ws(std::min<uint64_t>(cnt, per), h, lam);
-  if (w->dig_levels < nlev) {
+  const RangeWideWs ws = pl.wide_ws(cnt);
+  if (w->dig_levels < pl.gkeys * nlev) {  // dig_levels stays the size of the buffer, as eval_wide_batch keeps it
     size_t have = (size_t)w->dig_levels * 65;
-    if (int rc = grow(&w->d_dig, &have, (size_t)nlev * 65, st)) return rc;
-    w->dig_levels = nlev;
+    if (int rc = grow(&w->d_dig, &have, (size_t)pl.gkeys * nlev * 65, st)) return rc;
+    w->dig_levels = (uint32_t)(pl.gkeys * nlev);
   }
   if (int rc = range_begin(p, L, ws.total, zero_blocks)) return rc;
-  // CW digest of the key, once per call: bytes [0,32) of each level's cw_s / cw_v, and cw_t
-  hipLaunchKernelGGL(k_cw_digest, dim3((4 * nlev + 255) / 256), dim3(256), 0, st, cwb, cwb + (size_t)nlev * lam,
-                     cwb + 2 * (size_t)nlev * lam, nlev, lam, (uint64_t)1, (uint64_t)0, 1u, (uint4*)w->d_dig,
-                     w->d_dig + (size_t)nlev * 64);
-  HIP_TRY(hipGetLastError());
-  phase_mark(p, L, 1);
-  const auto group = lam == 32 ? range_wide_group<true, RangeOneKey> : range_wide_group<false, RangeOneKey>;
-  for (uint64_t o = 0; o < cnt; o += per) {  // h = 0: cnt < 2^12, one group
-    const uint64_t n = std::min<uint64_t>(per, cnt - o);
-    if (int rc = group(p, L, nb, 1, party, cwb, s0, 0, 1, range_add(A.x, off + o), n, h, ws, ys + o * (uint64_t)lam))
-      return rc;
-  }
-  return range_end(p, L);
-}
-
-// The tree path at lambda = 16, N <= 16, on L.st: points [off, off + cnt) of the range in launch
-// groups of 2^28.  RangeStore: into ys (the output of point `off`).  RangeFold (h > 0): all groups
-// into the one row ys of 16 bytes, which the caller has zeroed; op holds the table from point `off`.
-extern "C++" template <class OUT>
-static int range_tree(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
-                      const RangeArg& A, uint64_t off, uint64_t cnt, uint32_t h, uint8_t* ys, bool zero_blocks,
-                      const OUT op) {
-  size_t buf_bytes;
-  const size_t ws = range_ws_bytes(1, std::min<uint64_t>(cnt, kRangeLaunch), h, &buf_bytes);
-  if (int rc = range_begin(p, L, ws, zero_blocks)) return rc;
+  const uint8_t* cwv = cwb + (size_t)nlev * K * lam;
+  const uint8_t* cwt = cwb + 2 * (size_t)nlev * K * lam;
+  // CW digest of nk keys, key-major, dig_t behind their rows: bytes [0,32) of each level's cw_s / cw_v, and cw_t
+  const auto digest = [&](uint64_t k0, uint64_t nk) {
+    hipLaunchKernelGGL(k_cw_digest, dim3((unsigned)((4 * nlev * nk + 255) / 256)), dim3(256), 0, st, cwb, cwv, cwt, nlev,
+                       lam, (uint64_t)K, k0, (uint32_t)nk, (uint4*)w->d_dig, w->d_dig + (size_t)nk * nlev * 64);
+    return hipGetLastError();
+  };
+  const bool once = nkeys == 1;  // a call's only key: its digest is built once, ahead of mark 1
+  if (once) HIP_TRY(digest(key0, 1));
   phase_mark(p, L, 1);
   const auto group =
-      p->kind == 0 ? range_group<RangeHirose, RangeOneKey, OUT> : range_group<RangeMmo, RangeOneKey, OUT>;
-  for (uint64_t o = 0; o < cnt; o += kRangeLaunch) {  // h = 0: cnt < 2^12, one pass
-    const uint64_t n = std::min<uint64_t>(kRangeLaunch, cnt - o);
-    if (int rc = group(p, L, nb, 1, party, cwb, s0, 0, 1, range_add(A.x, off + o), n, h, buf_bytes,
-                       OUT::kFold ? ys : ys + o * 16, op.at(o)))
-      return rc;
+      pl.per_lane ? (lam == 32 ? range_wide_group<true, RangeDigKeys> : range_wide_group<false, RangeDigKeys>)
+                  : (lam == 32 ? range_wide_group<true, RangeOneKey> : range_wide_group<false, RangeOneKey>);
+  for (uint64_t k0 = key0; k0 < key0 + nkeys; k0 += pl.gkeys) {
+    const uint64_t nk = std::min<uint64_t>(pl.gkeys, key0 + nkeys - k0);
+    if (!once) HIP_TRY(digest(k0, nk));
+    for (uint64_t o = 0; o < cnt; o += pl.per) {  // several keys to a group, or h = 0: cnt <= per, one pass
+      const uint64_t n = std::min<uint64_t>(pl.per, cnt - o);
+      if (int rc = group(p, L, nb, K, party, cwb, s0s, k0, nk, range_add(A.x, off + o), n, pl.h, ws,
+                         ys + ((k0 - key0) * cnt + o) * lam))
+        return rc;
+    }
   }
   return range_end(p, L);
 }
 
-// Points [off, off + cnt) of the range into ys (the output of point `off`), on L.st.  h: the
-// call's block height (range_levels of its whole count).  zero_blocks: first part of a call.
-static int range_launch(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
-                        const RangeArg& A, uint64_t off, uint64_t cnt, uint32_t h, uint8_t* ys, bool zero_blocks) {
-  hipStream_t st = L.st;
+// Key k of a K-key block into the single-key layout: the key at dk, its s0 at ds0 (the caller has
+// zeroed the key's padding).
+static int range_gather(dcf_prg* p, Lease& L, size_t nb, size_t K, uint64_t k, const uint8_t* cwb, const uint8_t* s0s,
+                        uint8_t* dk, uint8_t* ds0) {
   const size_t lam = p->lambda;
-  if (p->kind == 0 && lam >= 32 && nb <= 16)
-    return range_wide_launch(p, L, nb, party, cwb, s0, A, off, cnt, h, ys, zero_blocks);
-  if (lam != 16 || nb > 16) {  // no tree-sharing path: materialise the points, run eval
-    DevBuf xs;  // eval owns the workspace, so the points get their own buffer
-    const uint64_t chunk = std::min<uint64_t>(cnt, kRangeChunk);
-    HIP_TRY(xs.alloc(chunk * nb));
+  hipLaunchKernelGGL(k_rangemk_gather, dim3(8), dim3(256), 0, L.st, cwb, cwb + dcf_cwb_np1_offset(nb, lam, K), s0s,
+                     (uint64_t)K, k, (uint32_t)(8 * nb), (uint32_t)lam, (uint32_t)dcf_cwb_np1_offset(nb, lam, 1), dk, ds0);
+  HIP_TRY(hipGetLastError());
+  return DCF_OK;
+}
+
+// Points (no tree-sharing path): key by key, the points materialised kRangeChunk at a time and run
+// through eval.  One key is read in place; a key of a K-key block is gathered into the single-key
+// layout first.  eval owns the workspace, so the points and the gathered key get buffers of the
+// call's own, freed on return.
+static int range_materialise(dcf_prg* p, Lease& L, size_t nb, size_t K, uint64_t key0, uint64_t nkeys, int party,
+                             const uint8_t* cwb, const uint8_t* s0s, const RangeArg& A, uint64_t off, uint64_t cnt,
+                             uint8_t* ys) {
+  hipStream_t st = L.st;
+  const size_t lam = p->lambda, kb = align256(dcf_cwb_bytes(nb, lam, 1));
+  DevBuf xs, key;
+  const uint64_t chunk = std::min<uint64_t>(cnt, kRangeChunk);
+  HIP_TRY(xs.alloc(chunk * nb));
+  uint8_t* dk = nullptr;
+  if (K > 1) {
+    HIP_TRY(key.alloc(kb + lam));
+    dk = (uint8_t*)key.p;
+    HIP_TRY(hipMemsetAsync(dk, 0, kb + lam, st));
+  }
+  for (uint64_t k = key0; k < key0 + nkeys; ++k) {
+    if (dk)
+      if (int rc = range_gather(p, L, nb, K, k, cwb, s0s, dk, dk + kb)) return rc;
     for (uint64_t o = 0; o < cnt; o += chunk) {
       const uint64_t n = std::min<uint64_t>(chunk, cnt - o);
       if (int rc = range_points(A, nb, off + o, n, (uint8_t*)xs.p, st)) return rc;
-      if (int rc = eval_launch(p, L, nb, 1, n, party, cwb, s0, (const uint8_t*)xs.p, ys + o * lam)) return rc;
+      if (int rc = eval_launch(p, L, nb, 1, n, party, dk ? dk : cwb, dk ? dk + kb : s0s, (const uint8_t*)xs.p,
+                               ys + ((k - key0) * cnt + o) * lam))
+        return rc;
     }
-    HIP_TRY(hipStreamSynchronize(st));  // xs is freed on return
-    return DCF_OK;
   }
-  return range_tree(p, L, nb, party, cwb, s0, A, off, cnt, h, ys, zero_blocks, RangeStore{});
+  HIP_TRY(hipStreamSynchronize(st));  // xs and key are freed on return
+  return DCF_OK;
+}
+
+// The plan over keys [key0, key0 + nkeys) of the K-key block at cwb / s0s — no more keys than it was
+// made for — and points [off, off + cnt) of the range, on L.st: into ys, the output of point `off`
+// of key key0 (RangeFold: see range_tree).  A point sub-range takes one key.  zero_blocks: first
+// part of a call.
+extern "C++" template <class OUT>
+static int range_run(dcf_prg* p, Lease& L, const RangePlan& pl, size_t nb, size_t K, uint64_t key0, uint64_t nkeys,
+                     int party, const uint8_t* cwb, const uint8_t* s0s, const RangeArg& A, uint64_t off, uint64_t cnt,
+                     uint8_t* ys, bool zero_blocks, const OUT op) {
+  if ((off != 0 || cnt != pl.count) && nkeys != 1)
+    return fail(DCF_ERR_ARG, "range eval: a point sub-range takes one key");
+  if (OUT::kFold && !pl.fused) return fail(DCF_ERR_ARG, "range fold: the shape has no folding tail");
+  switch (pl.engine) {
+    case RangeEngine::Tree16:
+      return range_tree(p, L, pl, nb, K, key0, nkeys, party, cwb, s0s, A, off, cnt, ys, zero_blocks, op);
+    case RangeEngine::Wide:
+      return range_wide(p, L, pl, nb, K, key0, nkeys, party, cwb, s0s, A, off, cnt, ys, zero_blocks);
+    case RangeEngine::Points:
+      return range_materialise(p, L, nb, K, key0, nkeys, party, cwb, s0s, A, off, cnt, ys);
+  }
+  return fail(DCF_ERR_ARG, "range eval: no engine");
 }
 
 int dcf_eval_range_device(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
                           const uint8_t* x0, uint64_t count, uint8_t* ys, void* stream) {
-  if (int rc = check_range_args(p, n_bytes, party, cwb, s0, x0)) return rc;
+  if (int rc = RangeCall::check(p, n_bytes, party, cwb, s0, x0)) return rc;
   if (count == 0) return DCF_OK;
   if (!ys) return fail(DCF_ERR_ARG, "null buffer");
-  RangeArg A;
-  if (int rc = range_parse(n_bytes, x0, count, &A)) return rc;
-  DeviceGuard dg(p->device);
-  Lease L(p);
-  if (int rc = L.order((hipStream_t)stream)) return rc;
-  return range_launch(p, L, n_bytes, party, cwb, s0, A, 0, count, range_levels(n_bytes, count), ys, true);
+  RangeCall c;
+  if (int rc = c.open(p, n_bytes, x0, count, stream)) return rc;
+  const RangePlan pl = plan_range(p->kind, p->lambda, n_bytes, 1, count, RangeRule::OneKey);
+  return range_run(p, *c.L, pl, n_bytes, 1, 0, 1, party, cwb, s0, c.A, 0, count, ys, true, RangeStore{});
 }
 
 // The range over host buffers: chunks of outputs through the workspace's staging buffers on its
-// compute stream, one after the other (the key goes to the device once).
+// compute stream, one after the other (the key goes to the device once; one plan, of the whole count).
 static int host_range(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, size_t cwb_len,
                       const uint8_t* s0, const RangeArg& A, uint64_t count, uint8_t* ys) {
   Workspace* w = L.w;
@@ -2638,10 +2811,10 @@ static int host_range(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t*
   uint8_t* dy = dk + kb;
   HIP_TRY(hipMemcpyAsync(dk, cwb, cwb_len, hipMemcpyHostToDevice, L.st));
   HIP_TRY(hipMemcpyAsync(ds0, s0, lam, hipMemcpyHostToDevice, L.st));
-  const uint32_t h = range_levels(nb, count);
+  const RangePlan pl = plan_range(p->kind, lam, nb, 1, count, RangeRule::OneKey);
   for (uint64_t off = 0; off < count; off += chunk) {
     const uint64_t n = std::min<uint64_t>(chunk, count - off);
-    if (int rc = range_launch(p, L, nb, party, dk, ds0, A, off, n, h, dy, off == 0)) return rc;
+    if (int rc = range_run(p, L, pl, nb, 1, 0, 1, party, dk, ds0, A, off, n, dy, off == 0, RangeStore{})) return rc;
     HIP_TRY(hipMemcpyAsync(w->h_stage, dy, n * lam, hipMemcpyDeviceToHost, L.st));
     HIP_TRY(hipStreamSynchronize(L.st));
     memcpy(ys + off * lam, w->h_stage, n * lam);
@@ -2651,226 +2824,30 @@ static int host_range(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t*
 
 int dcf_eval_range(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, size_t cwb_len, const uint8_t* s0,
                    const uint8_t* x0, uint64_t count, uint8_t* ys, size_t ys_len) {
-  if (int rc = check_range_args(p, n_bytes, party, cwb, s0, x0)) return rc;
+  if (int rc = RangeCall::check(p, n_bytes, party, cwb, s0, x0)) return rc;
   const size_t lam = p->lambda;
   if (cwb_len != dcf_cwb_bytes(n_bytes, lam, 1))
     return fail(DCF_ERR_KEY, "key size does not match 8*N levels (lib.rs:165)");
   if (ys_len % lam != 0 || ys_len / lam != count) return fail(DCF_ERR_LEN, "ys length != count * lambda");
   if (count == 0) return DCF_OK;
   if (!ys) return fail(DCF_ERR_ARG, "null buffer");
-  RangeArg A;
-  if (int rc = range_parse(n_bytes, x0, count, &A)) return rc;
-  DeviceGuard dg(p->device);
-  if (!dg.ok) return fail(DCF_ERR_HIP, "hipSetDevice failed");
-  Lease L(p);
-  int rc = host_lease(L);
-  if (rc == DCF_OK) rc = host_range(p, L, n_bytes, party, cwb, cwb_len, s0, A, count, ys);
-  return host_finish(L, rc);
+  RangeCall c;
+  int rc = c.open(p, n_bytes, x0, count, nullptr, true);
+  if (!c.L) return rc;  // failed ahead of the lease
+  if (rc == DCF_OK) rc = host_range(p, *c.L, n_bytes, party, cwb, cwb_len, s0, c.A, count, ys);
+  return host_finish(*c.L, rc);
 }
 
-// ---- multi-key contiguous-range eval (kernels_range.h; DESIGN.md "Multi-key range eval") ----
-
-constexpr uint64_t kRangeMkDirectMax = 1ull << 12;  // fewer outputs than this in the whole call: h = 0
-
-// Height of the aligned blocks the multi-key tree path uses (documented in include/dcf_hip.h).
-static uint32_t rangemk_levels(size_t n_bytes, uint64_t num_keys, uint64_t count) {
-  if (count < (4ull << kFdTail)) return 0;  // 2^h <= count / 4 needs h >= kFdTail = 4
-  const uint64_t small = (kRangeMkDirectMax + count - 1) / count;  // K * count < 2^12 <=> K < ceil(2^12 / count)
-  if (num_keys < small) return 0;
-  const uint32_t lg = 63u - (uint32_t)__builtin_clzll(count);
-  const uint32_t h = std::min<uint32_t>(kRangeMaxH, lg - 2u);  // >= kFdTail: count >= 64
-  return (uint32_t)std::min<uint64_t>(h, 8 * (uint64_t)n_bytes);
-}
-
-// Whole keys per launch group: every key has at most (count >> h) + 2 blocks of 2^h leaves.
-static uint64_t rangemk_keys_per_launch(uint32_t h, uint64_t count) {
-  const uint64_t maxroots = (count >> h) + 2;
-  if (maxroots > (kRangeLaunch >> h)) return 1;  // one key alone is more than a launch
-  return std::max<uint64_t>(1, kRangeLaunch / (maxroots << h));
-}
-
-int dcf_eval_range_multikey_subtree_levels(size_t n_bytes, size_t num_keys, uint64_t count) {
-  return n_bytes && num_keys ? (int)rangemk_levels(n_bytes, num_keys, count) : 0;
-}
-
-size_t dcf_eval_range_keys_per_launch(size_t n_bytes, size_t num_keys, uint64_t count) {
-  if (!n_bytes || !count) return 1;
-  return (size_t)rangemk_keys_per_launch(rangemk_levels(n_bytes, std::max<size_t>(num_keys, 1), count), count);
-}
-
-// ---- K keys over the Hirose PRG at lambda >= 32, N <= 16 (kernels_range_wide.h under RangeDigKeys) ----
-
-// Height of the blocks (documented in include/dcf_hip.h): the single-key rule from 2^12 points per
-// key, where a key has at least 16 blocks of its own; below, the multi-key rule.
-static uint32_t rangemk_wide_levels(size_t n_bytes, uint64_t num_keys, uint64_t count) {
-  return count >= kRangeDirectMax ? range_levels(n_bytes, count) : rangemk_levels(n_bytes, num_keys, count);
-}
-
-// Whole keys per launch group at height h; 1 when the keys run one after another (a key of more
-// than kWideBatchPpk points, or one that exceeds a group alone).
-static uint64_t rangemk_wide_keys(size_t n_bytes, uint64_t count, uint32_t h) {
-  const uint64_t span = ((count >> h) + 2) << h;  // a key's leaves, clipped ones included, at most
-  if (count > kWideBatchPpk || span > range_wide_points(n_bytes)) return 1;
-  const uint64_t rpk = (count + kTailPts - 1) / kTailPts;  // launch_tail's grid rows per key (launch_tail2: 1)
-  const uint64_t kdig = std::max<uint64_t>(1, (0xFFFFFFFFull / 4u) / (8 * n_bytes));  // as eval_wide_batch
-  return std::max<uint64_t>(
-      1, std::min<uint64_t>({range_wide_points(n_bytes) / span, kWideBatchKeys, 8 * kWideBatchKeys / rpk, kdig}));
-}
-static bool rangemk_wide_grouped(size_t n_bytes, uint64_t count, uint32_t h) {
-  return count <= kWideBatchPpk && (((count >> h) + 2) << h) <= range_wide_points(n_bytes);
-}
-
-int dcf_eval_range_wide_multikey_subtree_levels(size_t n_bytes, size_t num_keys, uint64_t count) {
-  if (!n_bytes || n_bytes > 16 || !num_keys || !count) return 0;
-  return (int)rangemk_wide_levels(n_bytes, num_keys, count);
-}
-
-size_t dcf_eval_range_wide_keys_per_launch(size_t n_bytes, size_t lambda, size_t num_keys, uint64_t count) {
-  if (!n_bytes || n_bytes > 16 || !num_keys || !count || lambda < 32) return 0;
-  return (size_t)rangemk_wide_keys(n_bytes, count, rangemk_wide_levels(n_bytes, num_keys, count));
-}
-
-// The call: launch groups of whole keys under the per-lane key policy, or — when a group holds
-// less than a key — the keys one after another through the single-key kernels, each read in place
-// from the K-key block, with the groups of range_wide_launch.  On L.st throughout: no gather, no
-// buffer of the call's own, no stream wait.  Keys [key0, key0 + nkeys) of the K-key block into ys (the
-// first output of key key0); zero_blocks: first part of a call.
-static int rangemk_wide(dcf_prg* p, Lease& L, size_t nb, size_t K, uint64_t key0, uint64_t nkeys, int party,
-                        const uint8_t* cwb, const uint8_t* s0s, const RangeArg& A, uint64_t count, uint8_t* ys,
-                        bool zero_blocks) {
-  hipStream_t st = L.st;
-  Workspace* w = L.w;
-  const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * nb);
-  const uint32_t h = rangemk_wide_levels(nb, nkeys, count);
-  const bool grouped = rangemk_wide_grouped(nb, count, h);
-  const uint64_t per = range_wide_points(nb);
-  const uint64_t kp = grouped ? std::min<uint64_t>(nkeys, rangemk_wide_keys(nb, count, h)) : 1;
-  const RangeWideWs ws =
-      range_wide_ws(std::min<uint64_t>(count, per), h, lam, kp, grouped ? kRangeWideTailKeys : kRangeWideTail);
-  if (w->dig_levels < kp * nlev) {  // dig_levels stays the size of the buffer, as eval_wide_batch keeps it
-    size_t have = (size_t)w->dig_levels * 65;
-    if (int rc = grow(&w->d_dig, &have, (size_t)kp * nlev * 65, st)) return rc;
-    w->dig_levels = (uint32_t)(kp * nlev);
-  }
-  if (int rc = range_begin(p, L, ws.total, zero_blocks)) return rc;
-  phase_mark(p, L, 1);
-  const uint8_t* cwv = cwb + (size_t)nlev * K * lam;
-  const uint8_t* cwt = cwb + 2 * (size_t)nlev * K * lam;
-  const auto digest = [&](uint64_t k0, uint64_t nk) {  // key-major, dig_t behind the nk keys' rows
-    hipLaunchKernelGGL(k_cw_digest, dim3((unsigned)((4 * nlev * nk + 255) / 256)), dim3(256), 0, st, cwb, cwv, cwt, nlev,
-                       lam, (uint64_t)K, k0, (uint32_t)nk, (uint4*)w->d_dig, w->d_dig + (size_t)nk * nlev * 64);
-    return hipGetLastError();
-  };
-  if (grouped) {
-    const auto group = lam == 32 ? range_wide_group<true, RangeDigKeys> : range_wide_group<false, RangeDigKeys>;
-    for (uint64_t k0 = key0; k0 < key0 + nkeys; k0 += kp) {
-      const uint64_t nk = std::min<uint64_t>(kp, key0 + nkeys - k0);
-      HIP_TRY(digest(k0, nk));
-      if (int rc = group(p, L, nb, K, party, cwb, s0s, k0, nk, A.x, count, h, ws, ys + (k0 - key0) * count * lam))
-        return rc;
-    }
-  } else {
-    const auto group = lam == 32 ? range_wide_group<true, RangeOneKey> : range_wide_group<false, RangeOneKey>;
-    for (uint64_t k = key0; k < key0 + nkeys; ++k) {
-      HIP_TRY(digest(k, 1));
-      for (uint64_t o = 0; o < count; o += per) {
-        const uint64_t n = std::min<uint64_t>(per, count - o);
-        if (int rc = group(p, L, nb, K, party, cwb, s0s, k, 1, range_add(A.x, o), n, h, ws,
-                           ys + ((k - key0) * count + o) * lam))
-          return rc;
-      }
-    }
-  }
-  return range_end(p, L);
-}
-
-// The slow path (the MMO PRG at lambda >= 32, N > 16): key by key, each gathered into the single-key
-// layout in a buffer of the call's own and run through the single-key range path.  Keys
-// [key0, key0 + nkeys) of the K-key block into ys (the first output of key key0).
-static int rangemk_fallback(dcf_prg* p, Lease& L, size_t nb, size_t K, uint64_t key0, uint64_t nkeys, int party,
-                            const uint8_t* cwb, const uint8_t* s0s, const RangeArg& A, uint64_t count, uint8_t* ys,
-                            bool zero_blocks) {
-  const size_t lam = p->lambda;
-  const size_t kb = align256(dcf_cwb_bytes(nb, lam, 1));
-  DevBuf key;  // range_launch's eval owns the workspace
-  HIP_TRY(key.alloc(kb + lam));
-  uint8_t* dk = (uint8_t*)key.p;
-  HIP_TRY(hipMemsetAsync(dk, 0, kb + lam, L.st));
-  const uint8_t* np1 = cwb + dcf_cwb_np1_offset(nb, lam, K);
-  const uint32_t h = range_levels(nb, count);
-  for (uint64_t k = key0; k < key0 + nkeys; ++k) {
-    hipLaunchKernelGGL(k_rangemk_gather, dim3(8), dim3(256), 0, L.st, cwb, np1, s0s, (uint64_t)K, k,
-                       (uint32_t)(8 * nb), (uint32_t)lam, (uint32_t)dcf_cwb_np1_offset(nb, lam, 1), dk, dk + kb);
-    HIP_TRY(hipGetLastError());
-    if (int rc = range_launch(p, L, nb, party, dk, dk + kb, A, 0, count, h, ys + (k - key0) * count * lam,
-                              zero_blocks && k == key0))
-      return rc;
-  }
-  HIP_TRY(hipStreamSynchronize(L.st));  // `key` is freed on return
-  return DCF_OK;
-}
-
-// The tree path at lambda = 16, N <= 16, on L.st: keys [key0, key0 + nkeys) of the K-key block in
-// launch groups of whole keys (or of 2^28 outputs of one key) at block height h.  RangeStore: into
-// ys, the first output of key key0.  RangeFold (h > 0): ys is row key0 of the call's `out`, 16
-// bytes per key, zeroed by the caller: the groups of one key fold into the same row.
-extern "C++" template <class OUT>
-static int rangemk_tree(dcf_prg* p, Lease& L, size_t nb, size_t K, uint64_t key0, uint64_t nkeys, int party,
-                        const uint8_t* cwb, const uint8_t* s0s, const RangeArg& A, uint64_t count, uint32_t h,
-                        uint8_t* ys, bool zero_blocks, const OUT op) {
-  const uint64_t per = std::min<uint64_t>(nkeys, rangemk_keys_per_launch(h, count));
-  const uint64_t row = OUT::kFold ? 1 : count;  // rows of ys per key
-  size_t buf_bytes;
-  const size_t ws = range_ws_bytes(per, std::min<uint64_t>(count, kRangeLaunch), h, &buf_bytes);
-  if (int rc = range_begin(p, L, ws, zero_blocks)) return rc;
-  phase_mark(p, L, 1);
-  const auto group = p->kind == 0 ? range_group<RangeHirose, RangeKeys, OUT> : range_group<RangeMmo, RangeKeys, OUT>;
-  if ((count >> h) + 2 <= (kRangeLaunch >> h)) {  // groups of whole keys
-    for (uint64_t k0 = key0; k0 < key0 + nkeys; k0 += per) {
-      const uint64_t keys = std::min<uint64_t>(per, key0 + nkeys - k0);
-      if (int rc = group(p, L, nb, K, party, cwb, s0s, k0, keys, A.x, count, h, buf_bytes, ys + (k0 - key0) * row * 16, op))
-        return rc;
-    }
-  } else {  // one key alone exceeds a launch: the keys one after another, 2^28 outputs at a time
-    for (uint64_t k = key0; k < key0 + nkeys; ++k)
-      for (uint64_t o = 0; o < count; o += kRangeLaunch) {
-        const uint64_t n = std::min<uint64_t>(kRangeLaunch, count - o);
-        if (int rc = group(p, L, nb, K, party, cwb, s0s, k, 1, range_add(A.x, o), n, h, buf_bytes,
-                           ys + ((k - key0) * row + (OUT::kFold ? 0 : o)) * 16, op.at(o)))
-          return rc;
-      }
-  }
-  return range_end(p, L);
-}
-
-// dcf_eval_range_multikey_device's paths over keys [key0, key0 + nkeys) of the K-key block, into ys
-// (the first output of key key0), on L.st; the heights and groups are those of a call of nkeys keys.
-static int rangemk_run(dcf_prg* p, Lease& L, size_t nb, size_t K, uint64_t key0, uint64_t nkeys, int party,
-                       const uint8_t* cwb, const uint8_t* s0s, const RangeArg& A, uint64_t count, uint8_t* ys,
-                       bool zero_blocks) {
-#ifndef DCF_RANGEMK_WIDE
-#define DCF_RANGEMK_WIDE 1  // A/B knob: 0 sends these shapes key by key through rangemk_fallback, as before
-#endif
-  if (DCF_RANGEMK_WIDE && p->kind == 0 && p->lambda >= 32 && nb <= 16)
-    return rangemk_wide(p, L, nb, K, key0, nkeys, party, cwb, s0s, A, count, ys, zero_blocks);
-  if (p->lambda != 16 || nb > 16)
-    return rangemk_fallback(p, L, nb, K, key0, nkeys, party, cwb, s0s, A, count, ys, zero_blocks);
-  return rangemk_tree(p, L, nb, K, key0, nkeys, party, cwb, s0s, A, count, rangemk_levels(nb, nkeys, count), ys,
-                      zero_blocks, RangeStore{});
-}
-
+// K keys over one range (DESIGN.md "Multi-key range eval"): the heights and groups of the multi-key rule.
 int dcf_eval_range_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, int party, const uint8_t* cwb,
                                    const uint8_t* s0s, const uint8_t* x0, uint64_t count, uint8_t* ys, void* stream) {
-  if (int rc = check_range_args(p, n_bytes, party, cwb, s0s, x0)) return rc;
-  if (n_bytes > 16 + kRangeTopMax) return fail(DCF_ERR_UNSUPPORTED, "range eval: N <= 256");
+  if (int rc = RangeCall::check(p, n_bytes, party, cwb, s0s, x0)) return rc;
   if (num_keys == 0 || count == 0) return DCF_OK;
   if (!ys) return fail(DCF_ERR_ARG, "null buffer");
-  RangeArg A;
-  if (int rc = range_parse(n_bytes, x0, count, &A)) return rc;
-  DeviceGuard dg(p->device);
-  Lease L(p);
-  if (int rc = L.order((hipStream_t)stream)) return rc;
-  return rangemk_run(p, L, n_bytes, num_keys, 0, num_keys, party, cwb, s0s, A, count, ys, true);
+  RangeCall c;
+  if (int rc = c.open(p, n_bytes, x0, count, stream)) return rc;
+  const RangePlan pl = plan_range(p->kind, p->lambda, n_bytes, num_keys, count, RangeRule::MultiKey);
+  return range_run(p, *c.L, pl, n_bytes, num_keys, 0, num_keys, party, cwb, s0s, c.A, 0, count, ys, true, RangeStore{});
 }
 
 // ---- range fold (kernels_range.h; DESIGN.md "Range fold") ----
@@ -2898,19 +2875,19 @@ static int fold_rows(const dcf_prg* p, const uint8_t* rows, const uint8_t* w, ui
   return DCF_OK;
 }
 
-// One key without a folding tail: the range path in passes of fold_pass_rows outputs into the
-// workspace's fold buffer (behind `reserve` bytes of it that the caller uses), each folded into
-// `out` (zeroed by the caller).  zero_blocks: first part of a call.
-static int fold_passes(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* cwb, const uint8_t* s0,
-                       const RangeArg& A, uint64_t count, const uint8_t* w, uint8_t* out, size_t reserve,
-                       bool zero_blocks) {
+// One key without a folding tail (pl: its single-key plan): the range in passes of fold_pass_rows
+// outputs into the workspace's fold buffer (behind `reserve` bytes of it that the caller uses), each
+// folded into `out` (zeroed by the caller).  zero_blocks: first part of a call.
+static int fold_passes(dcf_prg* p, Lease& L, const RangePlan& pl, size_t nb, int party, const uint8_t* cwb,
+                       const uint8_t* s0, const RangeArg& A, uint64_t count, const uint8_t* w, uint8_t* out,
+                       size_t reserve, bool zero_blocks) {
   const size_t lam = p->lambda;
   const uint64_t pass = std::min<uint64_t>(count, fold_pass_rows(lam));
   uint8_t* ys = L.w->d_fold + reserve;
-  const uint32_t h = range_levels(nb, count);
   for (uint64_t o = 0; o < count; o += pass) {
     const uint64_t n = std::min<uint64_t>(pass, count - o);
-    if (int rc = range_launch(p, L, nb, party, cwb, s0, A, o, n, h, ys, zero_blocks && o == 0)) return rc;
+    if (int rc = range_run(p, L, pl, nb, 1, 0, 1, party, cwb, s0, A, o, n, ys, zero_blocks && o == 0, RangeStore{}))
+      return rc;
     if (int rc = fold_rows(p, ys, w ? w + o * lam : nullptr, 1, n, out, L.st)) return rc;
   }
   return DCF_OK;
@@ -2918,56 +2895,48 @@ static int fold_passes(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t
 
 static int ensure_fold(Workspace* w, size_t bytes, hipStream_t st) { return grow(&w->d_fold, &w->fold_bytes, bytes, st); }
 
-// Is the shape fused — does the range call take the lambda = 16 tree path with h > 0?
-static bool fold_fused(const dcf_prg* p, size_t nb, uint32_t h) { return p->lambda == 16 && nb <= 16 && h > 0; }
-
 int dcf_eval_range_fold_device(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
                                const uint8_t* x0, uint64_t count, const uint8_t* w, uint8_t* out, void* stream) {
-  if (int rc = check_range_args(p, n_bytes, party, cwb, s0, x0)) return rc;
-  if (n_bytes > 16 + kRangeTopMax) return fail(DCF_ERR_UNSUPPORTED, "range eval: N <= 256");
+  if (int rc = RangeCall::check(p, n_bytes, party, cwb, s0, x0)) return rc;
   if (!out) return fail(DCF_ERR_ARG, "null buffer");
-  RangeArg A;
-  if (count)
-    if (int rc = range_parse(n_bytes, x0, count, &A)) return rc;
+  RangeCall c;
+  if (int rc = c.open(p, n_bytes, x0, count, stream)) return rc;
+  Lease& L = *c.L;
   const size_t lam = p->lambda;
-  DeviceGuard dg(p->device);
-  Lease L(p);
-  if (int rc = L.order((hipStream_t)stream)) return rc;
   HIP_TRY(hipMemsetAsync(out, 0, lam, L.st));
   if (count == 0) return DCF_OK;
-  const uint32_t h = range_levels(n_bytes, count);
-  if (fold_fused(p, n_bytes, h))
-    return range_tree(p, L, n_bytes, party, cwb, s0, A, 0, count, h, out, true, RangeFold{(const uint4*)w});
+  const RangePlan pl = plan_range(p->kind, lam, n_bytes, 1, count, RangeRule::OneKey);
+  if (pl.fused)
+    return range_run(p, L, pl, n_bytes, 1, 0, 1, party, cwb, s0, c.A, 0, count, out, true, RangeFold{(const uint4*)w});
   if (int rc = ensure_fold(L.w, std::min<uint64_t>(count, fold_pass_rows(lam)) * lam, L.st)) return rc;
-  return fold_passes(p, L, n_bytes, party, cwb, s0, A, count, w, out, 0, true);
+  return fold_passes(p, L, pl, n_bytes, party, cwb, s0, c.A, count, w, out, 0, true);
 }
 
 int dcf_eval_range_fold_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, int party, const uint8_t* cwb,
                                         const uint8_t* s0s, const uint8_t* x0, uint64_t count, const uint8_t* w,
                                         uint8_t* out, void* stream) {
-  if (int rc = check_range_args(p, n_bytes, party, cwb, s0s, x0)) return rc;
-  if (n_bytes > 16 + kRangeTopMax) return fail(DCF_ERR_UNSUPPORTED, "range eval: N <= 256");
+  if (int rc = RangeCall::check(p, n_bytes, party, cwb, s0s, x0)) return rc;
   if (num_keys == 0) return DCF_OK;
   if (!out) return fail(DCF_ERR_ARG, "null buffer");
-  RangeArg A;
-  if (count)
-    if (int rc = range_parse(n_bytes, x0, count, &A)) return rc;
+  RangeCall c;
+  if (int rc = c.open(p, n_bytes, x0, count, stream)) return rc;
+  Lease& L = *c.L;
+  const RangeArg& A = c.A;
   const size_t lam = p->lambda, K = num_keys;
-  DeviceGuard dg(p->device);
-  Lease L(p);
-  if (int rc = L.order((hipStream_t)stream)) return rc;
   HIP_TRY(hipMemsetAsync(out, 0, K * lam, L.st));
   if (count == 0) return DCF_OK;
-  const uint32_t h = rangemk_levels(n_bytes, K, count);
-  if (fold_fused(p, n_bytes, h))
-    return rangemk_tree(p, L, n_bytes, K, 0, K, party, cwb, s0s, A, count, h, out, true, RangeFold{(const uint4*)w});
+  const RangePlan all = plan_range(p->kind, lam, n_bytes, K, count, RangeRule::MultiKey);
+  if (all.fused)
+    return range_run(p, L, all, n_bytes, K, 0, K, party, cwb, s0s, A, 0, count, out, true, RangeFold{(const uint4*)w});
   const uint64_t rows = fold_pass_rows(lam);
-  if (count <= rows) {  // passes of whole keys
+  if (count <= rows) {  // passes of whole keys, each planned as a call of its own keys
     const uint64_t per = std::min<uint64_t>(K, rows / count);
     if (int rc = ensure_fold(L.w, per * count * lam, L.st)) return rc;
     for (uint64_t k0 = 0; k0 < K; k0 += per) {
       const uint64_t nk = std::min<uint64_t>(per, K - k0);
-      if (int rc = rangemk_run(p, L, n_bytes, K, k0, nk, party, cwb, s0s, A, count, L.w->d_fold, k0 == 0)) return rc;
+      const RangePlan pl = plan_range(p->kind, lam, n_bytes, nk, count, RangeRule::MultiKey);
+      if (int rc = range_run(p, L, pl, n_bytes, K, k0, nk, party, cwb, s0s, A, 0, count, L.w->d_fold, k0 == 0, RangeStore{}))
+        return rc;
       if (int rc = fold_rows(p, L.w->d_fold, w, nk, count, out + k0 * lam, L.st)) return rc;
     }
     return DCF_OK;
@@ -2977,12 +2946,10 @@ int dcf_eval_range_fold_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_k
   if (int rc = ensure_fold(L.w, reserve + rows * lam, L.st)) return rc;
   uint8_t* dk = L.w->d_fold;
   HIP_TRY(hipMemsetAsync(dk, 0, reserve, L.st));
-  const uint8_t* np1 = cwb + dcf_cwb_np1_offset(n_bytes, lam, K);
+  const RangePlan one = plan_range(p->kind, lam, n_bytes, 1, count, RangeRule::OneKey);
   for (uint64_t k = 0; k < K; ++k) {
-    hipLaunchKernelGGL(k_rangemk_gather, dim3(8), dim3(256), 0, L.st, cwb, np1, s0s, (uint64_t)K, k,
-                       (uint32_t)(8 * n_bytes), (uint32_t)lam, (uint32_t)dcf_cwb_np1_offset(n_bytes, lam, 1), dk, dk + kb);
-    HIP_TRY(hipGetLastError());
-    if (int rc = fold_passes(p, L, n_bytes, party, dk, dk + kb, A, count, w, out + k * lam, reserve, k == 0)) return rc;
+    if (int rc = range_gather(p, L, n_bytes, K, k, cwb, s0s, dk, dk + kb)) return rc;
+    if (int rc = fold_passes(p, L, one, n_bytes, party, dk, dk + kb, A, count, w, out + k * lam, reserve, k == 0)) return rc;
   }
   return DCF_OK;
 }

@@ -46,6 +46,26 @@ def test_subtree_levels_work_bound_shape(hip_lib):
     assert 2 + 2 * (128 - h) / 2 ** h + 4 * 2 ** h / count < 3
 
 
+def test_introspection_exports_match_recorded_table(hip_lib, golden):
+    """The six exports read a plan (plan_range); tests/golden/range_plan_table.json holds what they
+    returned over this grid when each computed its own arithmetic, recorded from that build."""
+    t = golden("range_plan_table")
+    g = t["grid"]
+    assert g == {"n_bytes": [1, 2, 4, 16, 17], "count": [1, 63, 64, 4095, 4096, 1 << 20, (1 << 28) + 1],
+                 "num_keys": [1, 2, 41, 4096], "lambda": [16, 32, 64]}
+    assert len(t["rows"]) == len(g["n_bytes"]) * len(g["count"]) * len(g["num_keys"]) * len(g["lambda"])
+    assert {tuple(r[:4]) for r in t["rows"]} == {(nb, c, K, lam) for nb in g["n_bytes"] for c in g["count"]
+                                                  for K in g["num_keys"] for lam in g["lambda"]}
+    for nb, c, K, lam, *want in t["rows"]:
+        got = [hip_lib.dcf_eval_range_subtree_levels(nb, c),
+               hip_lib.dcf_eval_range_wide_points_per_launch(nb, lam),
+               hip_lib.dcf_eval_range_multikey_subtree_levels(nb, K, c),
+               hip_lib.dcf_eval_range_keys_per_launch(nb, K, c),
+               hip_lib.dcf_eval_range_wide_multikey_subtree_levels(nb, K, c),
+               hip_lib.dcf_eval_range_wide_keys_per_launch(nb, lam, K, c)]
+        assert got == want, (nb, c, K, lam, t["columns"][4:])
+
+
 def test_range_argument_checks_without_gpu(hip_lib):
     assert hip_lib.dcf_eval_range_subtree_levels(0, 100) == 0
     x0 = ctypes.create_string_buffer(16)

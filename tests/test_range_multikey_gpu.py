@@ -81,9 +81,10 @@ def _check_blocks(blocks, nb, K, x0, count, h):
     assert 2 * K * (count - 1) <= blocks <= upper, (blocks, upper)
 
 
-def run_mk(dcf, nb, x0, count, K, seed, kind="hirose", lam=16, expect_h=None):
+def run_mk(dcf, nb, x0, count, K, seed, kind="hirose", lam=16, expect_h=None, both=False):
     """K fresh oracle keys, both parties.  Returns the prg, the DcfImpl, the oracle keys, the K-key
-    CWB, the party-1 seeds (device) and the party-1 outputs (K, count, lam)."""
+    CWB, the party-1 seeds (device) and the party-1 outputs (K, count, lam); with `both`, the seeds
+    and the outputs of both parties, and each party's block count behind them."""
     import torch
     rng = np.random.default_rng(seed)
     prg, P = _prgs(dcf, kind, lam, rng)
@@ -104,13 +105,14 @@ def run_mk(dcf, nb, x0, count, K, seed, kind="hirose", lam=16, expect_h=None):
     tree = kind == "hirose" and lam == 16 and nb <= 16
     if expect_h is not None:
         assert (h > 0) == expect_h, (nb, K, count, h)
-    ys, s0s = [], []
+    ys, s0s, blocks = [], [], []
     for b in (0, 1):
         s0 = _dev(b"".join(sd[b] for sd in seeds)).view(K, lam)
         buf = torch.full((K * count + 2 * PAD, lam), SENTINEL, dtype=torch.uint8, device="cuda")
         y = d.eval_range_multikey_device(bool(b), cwb, s0, x0, count, ys=buf[PAD:PAD + K * count].view(K, count, lam))
         torch.cuda.synchronize()
         assert y.shape == (K, count, lam)
+        blocks.append(prg.last_eval_blocks())
         assert bool((buf[:PAD] == SENTINEL).all()) and bool((buf[PAD + K * count:] == SENTINEL).all()), \
             ("neighbours of ys written", nb, x0, count, K, b)
         if tree and h:
@@ -128,7 +130,7 @@ def run_mk(dcf, nb, x0, count, K, seed, kind="hirose", lam=16, expect_h=None):
         m = idx < min(max(off, 0), count) if bounds[k] == 0 else idx > min(max(off, -1), count)
         bt = np.frombuffer(betas[k], np.uint8)
         assert (rec[k][m] == bt).all() and not rec[k][~m].any(), ("reconstruction", nb, hex(x0), count, "key", k)
-    return prg, d, oks, cwb, s0s[1], ys[1]
+    return (prg, d, oks, cwb, s0s, ys, blocks) if both else (prg, d, oks, cwb, s0s[1], ys[1])
 
 
 # ---- h = 0: every point walked on its own ----
@@ -189,6 +191,49 @@ def test_against_the_existing_paths(dcf):
         assert torch.equal(y1[k], single), k
     torch.cuda.synchronize()
     assert torch.equal(y1.reshape(K * count, 16), pointwise)
+
+
+K1_CASES = [  # engine, PRG, N, lambda, x0, count, (single-key h, multi-key h) or None where no tree runs
+    ("tree16", "hirose", 2, 16, 1001, 5000, (8, 10)),
+    ("tree16", "mmo", 2, 16, 1001, 5000, (8, 10)),
+    ("wide", "hirose", 2, 32, 1001, 5000, (8, 8)),
+    ("wide", "hirose", 2, 64, 1001, 5000, (8, 8)),
+    ("points", "hirose", 17, 16, (1 << 128) - 101, 300, None),
+    ("points", "mmo", 2, 32, 1001, 300, None),
+]
+
+
+@pytest.mark.parametrize("engine,kind,nb,lam,x0,count,hs", K1_CASES, ids=[f"{c[0]}-{c[1]}-{c[3]}" for c in K1_CASES])
+def test_one_key_multikey_call_equals_the_single_key_call(dcf, engine, kind, nb, lam, x0, count, hs):
+    """K = 1 through eval_range_multikey_device (run_mk: both parties, sentinels, the oracle on every
+    index) against eval_range_device on the same key, byte for byte, on each engine.  On the lambda =
+    16 tree path the two entry points use different heights and the multi-key call's blocks are those
+    of h = 10; at lambda >= 32 the heights agree and so do the block counts."""
+    import torch
+    seed = 1600 + 16 * nb + lam
+    prg, d, oks, _, s0s, ys, blocks = run_mk(dcf, nb, x0, count, 1, seed, kind=kind, lam=lam, both=True)
+    _, P = _prgs(dcf, kind, lam, np.random.default_rng(seed))  # the oracle prg of run_mk's keys
+    if hs:
+        wide = d.range_wide_multikey_subtree_levels(1, count) if engine == "wide" else d.range_multikey_subtree_levels(1, count)
+        assert (d.range_subtree_levels(count), wide) == hs
+    cwb1 = _dev(_cwb1(oks[0]))
+    xs = _points(nb, x0, np.arange(count))
+    for b in (0, 1):
+        buf = torch.full((count + 2 * PAD, lam), SENTINEL, dtype=torch.uint8, device="cuda")
+        y = d.eval_range_device(bool(b), cwb1, s0s[b][0], x0, count, ys=buf[PAD:PAD + count])
+        torch.cuda.synchronize()
+        single_blocks = prg.last_eval_blocks()
+        assert bool((buf[:PAD] == SENTINEL).all()) and bool((buf[PAD + count:] == SENTINEL).all()), (engine, kind, b)
+        assert torch.equal(y, ys[b][0]), (engine, kind, lam, b)
+        want = O.eval_(P, b, oks[0], s0s[b][0].cpu().numpy().tobytes(), xs, nthreads=8)
+        assert np.array_equal(y.cpu().numpy(), want), (engine, kind, lam, b)
+        if engine == "tree16" and kind == "hirose":
+            _check_blocks(blocks[b], nb, 1, x0, count, hs[1])
+        elif engine == "tree16":
+            from tests.test_range_mmo_gpu import check_blocks
+            check_blocks(blocks[b], nb, 1, x0, count, hs[1])
+        elif engine == "wide":
+            assert blocks[b] == single_blocks, (lam, b, blocks[b], single_blocks)
 
 
 def _single_cwb(cwb, nb, lam, K, k, dcf):

@@ -323,9 +323,10 @@ uint32_t prefix_split(uint32_t levels) { return levels > 18u ? 8u : (levels > 10
 
 // Depth-first tail of k_prefix_build16: the last H <= kPfxDfsMax levels, once the workgroup's
 // level holds at least one node per thread (2^10 = kBlock).
-// Full-domain eval: the last kFdTail levels in registers, depth-first (k_fd_dfs16; 5 levels:
-// 128 VGPRs + scratch spills), the levels above by one k_prefix_build16 launch.  Range eval: the
-// same tail below its breadth-first levels (k_range_tail16).
+// Full-domain eval's fast path (Hirose, from N = 2): the last kFdTail levels in registers, depth-first
+// (k_fd_dfs16; 5 levels: 128 VGPRs + scratch spills), the levels above by one k_prefix_build16 launch.
+// Range eval, and with it every other full-domain shape: the same tail below its breadth-first
+// levels (k_range_tail16).
 constexpr uint32_t kFdTail = 4;
 uint32_t prefix_dfs_levels(uint32_t levels, uint32_t S) {
   const uint32_t cap = kPfxDfsMax;
@@ -344,7 +345,7 @@ uint32_t prefix_dfs_levels(uint32_t levels, uint32_t S) {
 // auto cap.  C3 sweeps (2^28 points): r01q 24 519, 25 521, 26 524, 27 524 M evals/s; r05y (today's
 // walk, 2 runs, ms per step) 25 495.5 / 495.5, 26 491.6 / 492.0, 27 489.3 / 488.8, 28 488.9 / 488.8
 constexpr uint32_t kPrefixMax = 27;
-constexpr uint32_t kPrefixMaxForced = 28;  // dcf_prg_set_prefix_levels (Hirose 9.7 GB, MMO 2^28 x 33 B x 2 = 17.7 GB)
+constexpr uint32_t kPrefixMaxForced = 28;  // dcf_prg_set_prefix_levels (Hirose 9.7 GB, MMO 2^28 x 48 B = 12.9 GB)
 // Nodes per workgroup region of k_prefix_build16's two ping-pong buffers (log2): the widest
 // level a workgroup writes there.  With a depth-first tail of H levels the breadth-first part
 // stops at level D - H, so that is 2^(D-H-S) nodes (at D = 27: 553 MB of buffers beside the
@@ -356,7 +357,9 @@ uint32_t prefix_region_log2(uint32_t d, uint32_t S) {
 }
 
 // Device bytes of a shared-prefix table of depth d (table + build buffers, as build_prefix /
-// build_wide_prefix allocate them).
+// build_wide_prefix allocate them).  MMO, LAMBDA = 16: an upper bound — the depth rules and the
+// dcf_prg_set_prefix_max_bytes cap decide on the 66 B per row of the build's first layout; the rows
+// build_prefix allocates (the table and the level above it) take 48.
 size_t hirose16_table_bytes(uint32_t d) {  // Hirose, LAMBDA = 16: k_prefix_build16's table + buffers
   const uint32_t S = prefix_split(d);
   return ((((size_t)32 << d) + 255) & ~(size_t)255) +
@@ -388,7 +391,7 @@ uint32_t depth_rule(const dcf_prg* p, const Cfg& c, size_t n_bytes, uint32_t d, 
 uint32_t prefix_depth(const dcf_prg* p, const Cfg& c, size_t n_bytes, uint64_t num_keys, uint64_t total) {
   if (p->lambda != 16 || num_keys != 1 || c.prefix_levels == 0) return 0;
   // Hirose (one-launch build, k_prefix_build16): D = log2(total), r02g sweep C2 (2^24
-  // points) D = 22/23/24/25 -> 3.97/4.08/4.13/3.93 G evals/s; MMO (level kernels): log2 - 1
+  // points) D = 22/23/24/25 -> 3.97/4.08/4.13/3.93 G evals/s; MMO (a launch per level): log2 - 1
   const uint32_t lg = 63u - (uint32_t)__builtin_clzll(total | 1u);
   return depth_rule(p, c, n_bytes, p->kind == 0 ? lg : (lg > 1u ? lg - 1u : 0u), kPrefixMax, kPrefixMaxForced);
 }
@@ -671,25 +674,29 @@ int reserve_pfx(Workspace* w, size_t need, hipStream_t st, hipError_t* oom) {
   return DCF_OK;
 }
 
-// Expand the top `levels` levels of the key's tree (s = s0, v = 0, t = party at the
-// root; k_fd_level16 per level, as the full-domain eval does) into w->d_pfx.
+// Expand the top `levels` levels of the key's tree (s = s0, v = 0, t = party at the root) into
+// PrefixTable rows in w->d_pfx.  Hirose: one launch (k_prefix_build16).  MMO: the range path's kernels
+// on rows — the two nodes of level 1 walked from s0 (the root itself is no row: s0 is not masked),
+// then one k_range_level16 launch per level.
 // pst (reuse_prefix, Hirose only): the gated build, which runs only if the device state word says
 // that no table is valid; reuse_prefix sets the hints again afterwards.
-int build_prefix(dcf_prg* p, Workspace* w, size_t n_bytes, int party, const uint4* cws, const uint4* cwv,
-                 const uint8_t* cwt, const uint4* np1, const uint8_t* s0, uint32_t levels, PrefixTable* out,
-                 hipStream_t st, const uint32_t* pst = nullptr) {
+int build_prefix(dcf_prg* p, Workspace* w, int party, const uint4* cws, const uint4* cwv, const uint8_t* cwt,
+                 const uint4* np1, const uint8_t* s0, uint32_t levels, PrefixTable* out, hipStream_t st,
+                 const uint32_t* pst = nullptr) {
   w->ph.valid = false;  // d_pfx changes hands
-  const uint64_t maxnodes = 1ull << levels;
-  const size_t nodeb = 33, half = (maxnodes * nodeb + 255) & ~(size_t)255;
-  // Hirose: [table 2^D x 32 B | 2 x 2^S regions of 2^(D-1-S) nodes]; MMO: two level buffers + counters
+  // Hirose: [table 2^D x 32 B | 2 x 2^S regions of 2^(D-1-S) nodes]
+  // MMO: [table | the rows of level D - 1 | kPfxCtrs work counters, one per level launch | a block count]
   const uint32_t S = prefix_split(levels);
   const uint32_t R = 1u << prefix_region_log2(levels, S);
-  const size_t region = ((size_t)R * nodeb + 255) & ~(size_t)255;
-  const size_t tab_bytes = (maxnodes * 32 + 255) & ~(size_t)255;
-  const size_t need = p->kind == 0 ? tab_bytes + 2 * ((size_t)1 << S) * region : 2 * half + 64 * sizeof(uint32_t);
+  const size_t region = align256((size_t)R * 33);
+  const size_t tab_bytes = align256((size_t)32 << levels), half_bytes = align256((size_t)16 << levels);
+  constexpr size_t kPfxCtrs = 32;  // > kPrefixMaxForced
+  const size_t need = p->kind == 0 ? tab_bytes + 2 * ((size_t)1 << S) * region
+                                   : tab_bytes + half_bytes + (kPfxCtrs + 2) * sizeof(uint32_t);
   hipError_t oom;
   if (int rc = reserve_pfx(w, need, st, &oom)) return rc;
   if (oom != hipSuccess) return fail(kPrefixNoMem, std::string("prefix table: hipMalloc: ") + hipGetErrorString(oom));
+  *out = PrefixTable{(const uint4*)w->d_pfx, levels};
   if (p->kind == 0) {  // one launch: k_prefix_build16 (gated by the state word where there is one)
     uint8_t* ba = w->d_pfx + tab_bytes;
     const uint32_t H = prefix_dfs_levels(levels, S);
@@ -697,35 +704,28 @@ int build_prefix(dcf_prg* p, Workspace* w, size_t n_bytes, int party, const uint
                        p->d_tab, p->rk[0], cws, cwv, cwt, (const uint4*)s0, (uint32_t)party, S, levels, H, ba,
                        ba + ((size_t)1 << S) * region, (uint64_t)region, R, (uint4*)w->d_pfx, p->d_rk0, pst);
     HIP_TRY(hipGetLastError());
-    *out = PrefixTable{(const uint4*)w->d_pfx, levels};
     return DCF_OK;
   }
-  uint4* s_a = (uint4*)w->d_pfx;  // MMO (the Hirose PRG returned above): a launch per level
-  uint4* v_a = s_a + maxnodes;
-  uint8_t* t_a = (uint8_t*)(v_a + maxnodes);
-  uint4* s_b = (uint4*)(w->d_pfx + half);
-  uint4* v_b = s_b + maxnodes;
-  uint8_t* t_b = (uint8_t*)(v_b + maxnodes);
-  uint32_t* ctrs = (uint32_t*)(w->d_pfx + 2 * half);
-  HIP_TRY(hipMemsetAsync(ctrs, 0, 64 * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_fd_root16, dim3(1), dim3(64), 0, st, (const uint4*)s0, (uint32_t)party, s_a, v_a, t_a);
+  // Level l goes to the table's buffer when D - l is even and to the other one when it is odd, so
+  // level D lands in the table.  The kernels count their AES blocks: into a word of the build's own,
+  // since a table is no part of what dcf_prg_last_eval_blocks reports for the call.
+  uint4* cur = (uint4*)(w->d_pfx + ((levels - 1u) % 2u ? tab_bytes : 0));
+  uint4* nxt = (uint4*)(w->d_pfx + ((levels - 1u) % 2u ? 0 : tab_bytes));
+  uint32_t* ctrs = (uint32_t*)(w->d_pfx + tab_bytes + half_bytes);
+  unsigned long long* blocks = reinterpret_cast<unsigned long long*>(ctrs + kPfxCtrs);
+  HIP_TRY(hipMemsetAsync(ctrs, 0, (kPfxCtrs + 2) * sizeof(uint32_t), st));
+  hipLaunchKernelGGL((k_range_roots16_mmo<false, RangeOneKey>), dim3(1), dim3(kBlock), 0, st, p->d_tab, p->d_rk128, cws,
+                     cwv, cwt, np1, (const uint4*)s0, RangeOneKey{}, (uint32_t)party, RangeX{0, 0}, 1u, (uint64_t)2,
+                     cur, blocks);
   HIP_TRY(hipGetLastError());
-  const uint32_t nlev = (uint32_t)(8 * n_bytes);  // > levels: no level here is the last one
-  for (uint32_t lev = 0; lev < levels; ++lev) {
-    const uint64_t parents = 1ull << lev;
-    hipLaunchKernelGGL(k_fd_level16_mmo, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
-                       p->d_rk128, cws, cwv, cwt, np1, lev, nlev, parents, s_a, v_a, t_a, s_b, v_b, t_b,
-                       (uint4*)nullptr, ctrs + lev);
+  for (uint32_t lev = 1; lev < levels; ++lev) {  // the 2^lev parents of level lev
+    const uint32_t parents = 1u << lev;
+    hipLaunchKernelGGL((k_range_level16<RangeMmo, RangeOneKey>), dim3((unsigned)grid_for(parents, p->cus)),
+                       dim3(kBlock), 0, st, p->d_tab, p->d_rk128, cws, cwv, cwt, RangeOneKey{}, lev, parents,
+                       (const uint4*)cur, nxt, ctrs + lev, blocks);
     HIP_TRY(hipGetLastError());
-    std::swap(s_a, s_b);
-    std::swap(v_a, v_b);
-    std::swap(t_a, t_b);
+    std::swap(cur, nxt);
   }
-  // 32-byte rows (kernels16.h PrefixTable) into the other buffer: 2^D * 32 <= half.
-  hipLaunchKernelGGL(k_prefix_pack, dim3((unsigned)std::min<uint64_t>((maxnodes + 255) / 256, 4096)), dim3(256), 0,
-                     st, s_a, v_a, t_a, maxnodes, s_b);
-  HIP_TRY(hipGetLastError());
-  *out = PrefixTable{s_b, levels};
   return DCF_OK;
 }
 
@@ -737,7 +737,7 @@ int try_prefix(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, int party
                const uint32_t* pst = nullptr) {
   *out = PrefixTable{nullptr, 0u};
   while (d) {
-    const int rc = build_prefix(p, w, n_bytes, party, cws, cwv, cwt, np1, s0, d, out, st, pst);
+    const int rc = build_prefix(p, w, party, cws, cwv, cwt, np1, s0, d, out, st, pst);
     if (rc == DCF_OK) w->last_prefix = out->levels;
     if (rc != kPrefixNoMem) return rc;
     if (c.prefix_levels >= 0) return fail(DCF_ERR_HIP, t_err);  // a forced depth must fit
@@ -890,7 +890,7 @@ int reuse_prefix(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, int par
   // The key changed under the same pointers (state 0 after the check, or after a deepening that
   // found another depth than the host expected): rebuild at the first-call depth; else nothing runs.
   const Workspace::PrefixHints keep = h;  // (build_prefix clears the hints)
-  if (int rc = build_prefix(p, w, n_bytes, party, cws, cwv, cwt, np1, s0, keep.base, out, st, w->d_pst)) return rc;
+  if (int rc = build_prefix(p, w, party, cws, cwv, cwt, np1, s0, keep.base, out, st, w->d_pst)) return rc;
   launch_commit(w, st, 0u, keep.base, 0xFFFFFFFFu, counted * ((2ull << keep.base) - 2));
   HIP_TRY(hipGetLastError());
   h = keep;
@@ -2277,101 +2277,6 @@ int dcf_share_from_bincode(size_t n_bytes, size_t lambda, const uint8_t* in, siz
   return DCF_OK;
 }
 
-int dcf_eval_full_domain_device(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
-                                uint8_t* ys, void* stream) {
-  if (!p) return fail(DCF_ERR_ARG, "null prg");
-  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
-  if (n_bytes > 4) return fail(DCF_ERR_UNSUPPORTED, "full-domain eval: N <= 4 (2^32 outputs)");
-  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
-  if (!cwb || !s0 || !ys) return fail(DCF_ERR_ARG, "null buffer");
-  DeviceGuard dg(p->device);
-  Lease L(p);
-  if (int rc = L.order((hipStream_t)stream)) return rc;
-  hipStream_t st = L.st;
-  const uint32_t nlev = (uint32_t)(8 * n_bytes);
-  const uint64_t npts = 1ull << nlev;
-  const size_t lam = p->lambda;
-  if (lam != 16) {  // no tree sharing at LAMBDA >= 32: materialise the domain and run eval
-    DevBuf xs;  // eval_wide owns the workspace, so the points get their own buffer
-    HIP_TRY(xs.alloc(npts * n_bytes));
-    hipLaunchKernelGGL(k_domain_points, dim3(1024), dim3(256), 0, st, (uint32_t)n_bytes, npts, (uint8_t*)xs.p);
-    HIP_TRY(hipGetLastError());
-    int rc = eval_launch(p, L, n_bytes, 1, npts, party, cwb, s0, (const uint8_t*)xs.p, ys);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(st));  // xs is freed on return
-    return DCF_OK;
-  }
-  // Two ping-pong node buffers: s (16 B), v (16 B), t (1 B) per node.  With the
-  // Hirose PRG the last kFdTail levels run in registers (k_fd_dfs16), so the widest
-  // node level in HBM is 2^(n - kFdTail).
-  const bool fused = p->kind == 0 && nlev > kFdTail;
-  const size_t n = 8 * n_bytes;
-  const uint4* cws = (const uint4*)cwb;
-  const uint4* cwv = (const uint4*)(cwb + n * lam);
-  const uint8_t* cwt = cwb + 2 * n * lam;
-  const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(n_bytes, lam, 1));
-  const uint32_t lev_end = fused ? nlev - kFdTail : nlev;
-  // Hirose with the depth-first tail: levels 0 .. lev_end - 1 in ONE launch of the shared-prefix
-  // table build (k_prefix_build16: workgroup subtrees, a depth-first register tail, 32-byte rows)
-  // instead of one breadth-first level launch per level with 33-byte SoA nodes through HBM;
-  // the tail then starts from the rows.  Falls back to the level kernels if the table and its
-  // build buffers (~65 B per node of level lev_end) cannot be allocated.
-  if (fused && lev_end >= 12) {
-    PrefixTable pf{nullptr, 0u};
-    const int brc = build_prefix(p, L.w, n_bytes, party, cws, cwv, cwt, np1, s0, lev_end, &pf, st);
-    if (brc != DCF_OK && brc != kPrefixNoMem) return brc;
-    if (brc == DCF_OK) {
-      const uint64_t nodes = 1ull << lev_end;
-      if (int rc2 = ensure_ctr(L.w)) return rc2;
-      HIP_TRY(hipMemsetAsync(L.w->d_ctr, 0, kCtrBytes, st));
-      hipLaunchKernelGGL((k_fd_dfs16<kFdTail, true>), dim3((unsigned)grid_for(nodes, p->cus)), dim3(kBlock), 0, st,
-                         p->d_tab, p->rk[0], cws, cwv, cwt, np1, lev_end, nodes, pf.sv, (const uint4*)nullptr,
-                         (const uint8_t*)nullptr, (uint4*)ys, L.w->d_ctr);
-      HIP_TRY(hipGetLastError());
-      return DCF_OK;
-    }
-  }
-  const uint64_t maxnodes = fused ? (npts >> kFdTail) : npts / 2;
-  const size_t nodeb = 33;
-  // + one work counter per launch (64-node units, see next_wave_base) after the nodes
-  const size_t ctr_off = (2 * maxnodes * nodeb + 64 + 255) & ~(size_t)255;
-  int rc = ensure_ws(L.w, ctr_off + 64 * sizeof(uint32_t), st);
-  if (rc) return rc;
-  uint8_t* w = L.w->d_ws;
-  uint32_t* ctrs = (uint32_t*)(w + ctr_off);
-  HIP_TRY(hipMemsetAsync(ctrs, 0, 64 * sizeof(uint32_t), st));
-  uint4* s_a = (uint4*)w;
-  uint4* v_a = s_a + maxnodes;
-  uint8_t* t_a = (uint8_t*)(v_a + maxnodes);
-  uint4* s_b = (uint4*)(w + maxnodes * nodeb + 16 - (maxnodes * nodeb) % 16);
-  uint4* v_b = s_b + maxnodes;
-  uint8_t* t_b = (uint8_t*)(v_b + maxnodes);
-  hipLaunchKernelGGL(k_fd_root16, dim3(1), dim3(64), 0, st, (const uint4*)s0, (uint32_t)party, s_a, v_a, t_a);
-  HIP_TRY(hipGetLastError());
-  for (uint32_t lev = 0; lev < lev_end; ++lev) {
-    const uint64_t parents = 1ull << lev;
-    if (p->kind == 1)
-      hipLaunchKernelGGL(k_fd_level16_mmo, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
-                         p->d_rk128, cws, cwv, cwt, np1, lev, nlev, parents, s_a, v_a, t_a, s_b, v_b, t_b,
-                         (uint4*)ys, ctrs + lev);
-    else
-      hipLaunchKernelGGL(k_fd_level16, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
-                         p->rk[0], cws, cwv, cwt, np1, lev, nlev, parents, s_a, v_a, t_a, s_b, v_b, t_b, (uint4*)ys,
-                         ctrs + lev);
-    HIP_TRY(hipGetLastError());
-    std::swap(s_a, s_b);
-    std::swap(v_a, v_b);
-    std::swap(t_a, t_b);
-  }
-  if (fused) {
-    const uint64_t nodes = 1ull << lev_end;
-    hipLaunchKernelGGL(k_fd_dfs16<kFdTail>, dim3((unsigned)grid_for(nodes, p->cus)), dim3(kBlock), 0, st, p->d_tab,
-                       p->rk[0], cws, cwv, cwt, np1, lev_end, nodes, s_a, v_a, t_a, (uint4*)ys, ctrs + 63);
-    HIP_TRY(hipGetLastError());
-  }
-  return DCF_OK;
-}
-
 // ---- contiguous-range eval (kernels_range.h; DESIGN.md "Range eval") ----
 
 constexpr uint64_t kRangeChunk = 1ull << 22;  // points per pass of the materialising path
@@ -2795,6 +2700,94 @@ int dcf_eval_range_device(dcf_prg* p, size_t n_bytes, int party, const uint8_t* 
   if (int rc = c.open(p, n_bytes, x0, count, stream)) return rc;
   const RangePlan pl = plan_range(p->kind, p->lambda, n_bytes, 1, count, RangeRule::OneKey);
   return range_run(p, *c.L, pl, n_bytes, 1, 0, 1, party, cwb, s0, c.A, 0, count, ys, true, RangeStore{});
+}
+
+// Full domain over the MMO PRG at LAMBDA = 16: the root, then 8N breadth-first level launches
+// (k_fd_level16_mmo) between two SoA node buffers in d_ws — s (16 B), v (16 B), t (1 B) per node,
+// the widest level held 2^(8N - 1) — the last of which writes y.  The one user of that node format:
+// kept because the range route (16 launch groups with a register tail at N = 4) measured 204.0 ms
+// against these launches' 192.0 (profiles/r17).
+static int full_domain_mmo16(dcf_prg* p, Lease& L, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
+                             uint8_t* ys) {
+  hipStream_t st = L.st;
+  const uint32_t nlev = (uint32_t)(8 * n_bytes);
+  const size_t lam = 16, nodeb = 33;
+  const uint64_t maxnodes = (1ull << nlev) / 2;
+  const uint4* cws = (const uint4*)cwb;
+  const uint4* cwv = (const uint4*)(cwb + nlev * lam);
+  const uint8_t* cwt = cwb + 2 * nlev * lam;
+  const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(n_bytes, lam, 1));
+  // + one work counter per launch (64-node units, see next_wave_base) after the nodes
+  const size_t ctr_off = (2 * maxnodes * nodeb + 64 + 255) & ~(size_t)255;
+  if (int rc = ensure_ws(L.w, ctr_off + 64 * sizeof(uint32_t), st)) return rc;
+  uint8_t* w = L.w->d_ws;
+  uint32_t* ctrs = (uint32_t*)(w + ctr_off);
+  HIP_TRY(hipMemsetAsync(ctrs, 0, 64 * sizeof(uint32_t), st));
+  uint4* s_a = (uint4*)w;
+  uint4* v_a = s_a + maxnodes;
+  uint8_t* t_a = (uint8_t*)(v_a + maxnodes);
+  uint4* s_b = (uint4*)(w + maxnodes * nodeb + 16 - (maxnodes * nodeb) % 16);
+  uint4* v_b = s_b + maxnodes;
+  uint8_t* t_b = (uint8_t*)(v_b + maxnodes);
+  hipLaunchKernelGGL(k_fd_root16, dim3(1), dim3(64), 0, st, (const uint4*)s0, (uint32_t)party, s_a, v_a, t_a);
+  HIP_TRY(hipGetLastError());
+  for (uint32_t lev = 0; lev < nlev; ++lev) {
+    const uint64_t parents = 1ull << lev;
+    hipLaunchKernelGGL(k_fd_level16_mmo, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
+                       p->d_rk128, cws, cwv, cwt, np1, lev, nlev, parents, s_a, v_a, t_a, s_b, v_b, t_b, (uint4*)ys,
+                       ctrs + lev);
+    HIP_TRY(hipGetLastError());
+    std::swap(s_a, s_b);
+    std::swap(v_a, v_b);
+    std::swap(t_a, t_b);
+  }
+  return DCF_OK;
+}
+
+// The whole domain is the range [0, 2^(8N)), and but for two shapes full-domain eval is that range
+// call.  Hirose, LAMBDA = 16, from N = 2: levels 0 .. 8N - kFdTail - 1 in ONE launch of the
+// shared-prefix table build (k_prefix_build16: workgroup subtrees, no level launches), then the
+// register depth-first tail on its rows (k_fd_dfs16), which the range driver's root walk and level
+// launches do not match (DESIGN.md "Range eval": 1.26x at N = 4); when its table cannot be
+// allocated, it is a range call as well.  MMO, LAMBDA = 16: full_domain_mmo16.
+int dcf_eval_full_domain_device(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
+                                uint8_t* ys, void* stream) {
+  if (!p) return fail(DCF_ERR_ARG, "null prg");
+  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
+  if (n_bytes > 4) return fail(DCF_ERR_UNSUPPORTED, "full-domain eval: N <= 4 (2^32 outputs)");
+  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
+  if (!cwb || !s0 || !ys) return fail(DCF_ERR_ARG, "null buffer");
+  DeviceGuard dg(p->device);
+  Lease L(p);
+  if (int rc = L.order((hipStream_t)stream)) return rc;
+  hipStream_t st = L.st;
+  const uint32_t nlev = (uint32_t)(8 * n_bytes);
+  const size_t lam = p->lambda;
+  if (p->kind == 0 && lam == 16 && nlev >= kFdTail + 12) {
+    const uint32_t lev_end = nlev - kFdTail;
+    const uint4* cws = (const uint4*)cwb;
+    const uint4* cwv = (const uint4*)(cwb + nlev * lam);
+    const uint8_t* cwt = cwb + 2 * nlev * lam;
+    const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(n_bytes, lam, 1));
+    PrefixTable pf{nullptr, 0u};
+    const int brc = build_prefix(p, L.w, party, cws, cwv, cwt, np1, s0, lev_end, &pf, st);
+    if (brc != DCF_OK && brc != kPrefixNoMem) return brc;
+    if (brc == DCF_OK) {
+      const uint64_t nodes = 1ull << lev_end;
+      if (int rc2 = ensure_ctr(L.w)) return rc2;
+      HIP_TRY(hipMemsetAsync(L.w->d_ctr, 0, kCtrBytes, st));
+      hipLaunchKernelGGL(k_fd_dfs16<kFdTail>, dim3((unsigned)grid_for(nodes, p->cus)), dim3(kBlock), 0, st, p->d_tab,
+                         p->rk[0], cws, cwv, cwt, np1, lev_end, nodes, pf.sv, (uint4*)ys, L.w->d_ctr);
+      HIP_TRY(hipGetLastError());
+      return DCF_OK;
+    }
+  }
+  if (p->kind == 1 && lam == 16) return full_domain_mmo16(p, L, n_bytes, party, cwb, s0, ys);
+  const uint64_t npts = 1ull << nlev;
+  RangeArg A{};  // x0 = 0
+  A.first = npts;
+  const RangePlan pl = plan_range(p->kind, lam, n_bytes, 1, npts, RangeRule::OneKey);
+  return range_run(p, L, pl, n_bytes, 1, 0, 1, party, cwb, s0, A, 0, npts, ys, true, RangeStore{});
 }
 
 // The range over host buffers: chunks of outputs through the workspace's staging buffers on its

@@ -145,8 +145,8 @@ __global__ __launch_bounds__(kBlock, 1) void k_eval16(
 }
 
 // Shared prefix (single key): the walk's state after its first `levels` levels depends
-// only on those bits of x, so the host expands that top tree once (the full-domain
-// level kernels, k_fd_level16 / k_fd_level16_mmo) into a table indexed by the prefix, and a point
+// only on those bits of x, so the host expands that top tree once (build_prefix: k_prefix_build16,
+// or k_range_level16 level by level for the MMO PRG) into a table indexed by the prefix, and a point
 // starts at level `levels` from its table row.  levels = 0: no table.
 // Row i is 32 contiguous bytes, sv[2i] = s and sv[2i+1] = v, with t in s's bit 0 of
 // byte 15: below the root s is always masked there (s' = side & M ^ t*cw.s, and cw.s
@@ -423,87 +423,12 @@ __global__ __launch_bounds__(kBlock, 1) void k_prg16(const uint32_t* __restrict_
 
 namespace {
 
-// ------------------------------------------------------------------------
-// Full-domain eval at LAMBDA = 16: y for every x in [0, 2^n),
-// n = 8N, by breadth-first tree expansion.  One lane per parent node per
-// level: one PRG call (A, B) yields BOTH children, so the whole domain costs
-// 2 AES blocks per leaf instead of 2n per point.  Node state (s, v, t) lives in
-// SoA buffers indexed by the big-endian x prefix; the last level writes y.
-// Child rules are lib.rs:176-189 with x-bit 0 (left) / 1 (right).
-// ------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock, 1) void k_fd_level16(
-    const uint32_t* __restrict__ tab, const RoundKeys rk, const uint4* __restrict__ cw_s,
-    const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const uint4* __restrict__ cw_np1,
-    const uint32_t lev, const uint32_t nlev, const uint64_t nparents, const uint4* __restrict__ s_in,
-    const uint4* __restrict__ v_in, const uint8_t* __restrict__ t_in, uint4* __restrict__ s_out,
-    uint4* __restrict__ v_out, uint8_t* __restrict__ t_out, uint4* __restrict__ ys, uint32_t* __restrict__ ctr) {
-  __shared__ uint32_t lds[kLdsWords];
-  lds_fill_tables(lds, tab);
-  const uint32_t lc = lane_const();
-  const uint4 cs = cw_s[lev], cv = cw_v[lev], np = cw_np1[0];
-  const uint32_t ct = cw_t[lev];
-  const uint32_t csw[4] = {cs.x, cs.y, cs.z, cs.w}, cvw[4] = {cv.x, cv.y, cv.z, cv.w};
-  const uint32_t npw[4] = {np.x, np.y, np.z, np.w};
-  const bool last = lev + 1 == nlev;
-  const uint32_t unit = fd_unit(nparents);
-  for (uint64_t base = next_unit_base_n(ctr, ~0ull, unit); base < nparents;
-       base = next_unit_base_n(ctr, base, unit)) {
-    const uint64_t j = base + (threadIdx.x & 63u);
-    const bool live = j < nparents;
-    const uint64_t jj = live ? j : nparents - 1;
-    const uint4 sv = s_in[jj], vv = v_in[jj];
-    const uint32_t s[4] = {sv.x, sv.y, sv.z, sv.w}, v[4] = {vv.x, vv.y, vv.z, vv.w};
-    const uint32_t t = t_in[jj];
-    uint32_t st[2][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      st[0][k] = s[k];
-      st[1][k] = ~s[k];
-    }
-    aes256_tt<2>(st, rk, lds, lc);  // A, B
-    const uint32_t tm = 0u - t;
-    uint32_t sl[4], vl[4], sr[4], vr[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t msk = (k == 3) ? kMaskLast : 0xFFFFFFFFu;
-      sl[k] = ((st[0][k] ^ s[k]) & msk) ^ (tm & csw[k]);
-      sr[k] = (s[k] & msk) ^ (tm & csw[k]);
-      vl[k] = v[k] ^ ((st[1][k] ^ ~s[k]) & msk) ^ (tm & cvw[k]);
-      vr[k] = v[k] ^ ((~s[k]) & msk) ^ (tm & cvw[k]);
-    }
-    const uint32_t tl = ((st[0][0] ^ s[0]) & 1u) ^ (t & ct & 1u);
-    const uint32_t tr = ((st[1][0] ^ ~s[0]) & 1u) ^ (t & (ct >> 1) & 1u);
-    if (!live) continue;
-    if (last) {  // y = v ^ s ^ t * cw_np1 (lib.rs:192)
-      const uint32_t ml = 0u - tl, mr = 0u - tr;
-      ys[2 * j] = make_uint4(vl[0] ^ sl[0] ^ (ml & npw[0]), vl[1] ^ sl[1] ^ (ml & npw[1]),
-                             vl[2] ^ sl[2] ^ (ml & npw[2]), vl[3] ^ sl[3] ^ (ml & npw[3]));
-      ys[2 * j + 1] = make_uint4(vr[0] ^ sr[0] ^ (mr & npw[0]), vr[1] ^ sr[1] ^ (mr & npw[1]),
-                                 vr[2] ^ sr[2] ^ (mr & npw[2]), vr[3] ^ sr[3] ^ (mr & npw[3]));
-    } else {
-      s_out[2 * j] = make_uint4(sl[0], sl[1], sl[2], sl[3]);
-      s_out[2 * j + 1] = make_uint4(sr[0], sr[1], sr[2], sr[3]);
-      v_out[2 * j] = make_uint4(vl[0], vl[1], vl[2], vl[3]);
-      v_out[2 * j + 1] = make_uint4(vr[0], vr[1], vr[2], vr[3]);
-      t_out[2 * j] = (uint8_t)tl;
-      t_out[2 * j + 1] = (uint8_t)tr;
-    }
-  }
-}
-
-// Pack the prefix level's (s, v, t) arrays into PrefixTable rows.
-__global__ void k_prefix_pack(const uint4* __restrict__ s, const uint4* __restrict__ v,
-                              const uint8_t* __restrict__ t, const uint64_t n, uint4* __restrict__ sv) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    uint4 a = s[i];
-    a.w = (a.w & kMaskLast) | ((uint32_t)(t[i] & 1u) << 24);
-    sv[2 * i] = a;
-    sv[2 * i + 1] = v[i];
-  }
-}
-
-// One PRG call (A, B) on node (s, v, t) of level `lev` -> both children (lib.rs:176-189
-// with x bit 0 / 1), as in k_fd_level16.
+// Tree expansion at LAMBDA = 16 (the table builds, full-domain and range eval): one PRG
+// call (A = AES(s) ^ s, B = AES(~s) ^ ~s) on node (s, v, t) of level `lev` yields BOTH children, so a
+// whole subtree costs 2 AES blocks per leaf instead of 2n per point.  The child rules are
+// lib.rs:176-189 with x bit 0 (left) / 1 (right), M clearing bit 0 of byte 15 and tm = t ? ~0 : 0:
+//   s_l = (A & M) ^ tm & cw_s      v_l = v ^ (B & M) ^ tm & cw_v      t_l = A bit 0 ^ t & cw_tl
+//   s_r = (s & M) ^ tm & cw_s      v_r = v ^ (~s & M) ^ tm & cw_v     t_r = B bit 0 ^ t & cw_tr
 // GKB: round keys read per round from the device copy rkg (aes256_tt_gk) instead of SGPRs.
 template <bool GKB = false>
 __device__ __forceinline__ void fd_children(const uint32_t* lds, uint32_t lc, const RoundKeys& rk,
@@ -619,14 +544,14 @@ __global__ __launch_bounds__(kBlock, 1) void k_mk_prefix16(
 }
 
 // Shared-prefix table (PrefixTable rows) of depth D in ONE launch, Hirose PRG.
-// The level-by-level build (k_fd_level16, one launch per level) spends most of its time
+// A level-by-level build (one launch per level) spends most of its time
 // on the narrow upper levels (C2: 23 launches, ~1 ms of a 5 ms step).  Here workgroup w
 // (2^S of them) owns the subtree under node w of level S: wave 0 walks the root path to
 // it (S PRG calls, bits of w Msb-first), then the workgroup expands its subtree level
 // by level with workgroup barriers only (no grid-wide sync), nodes ping-ponging through
 // the workgroup's own regions of two buffers (SoA: s[R] | v[R] | t[R], R = 2^(D-1-S)),
 // and the last level writes packed 32-B rows of the workgroup's contiguous block of the
-// table directly (no pack pass).  Same bytes as the level kernels + k_prefix_pack.
+// table directly (no pack pass).
 // H > 0: the level-by-level part stops at level D - H (one node or more per thread) and
 // each thread expands its nodes' last H levels depth-first (see the tail below).
 // Round keys per round from the device copy (aes256_tt_gk: SGPR keys spill here).
@@ -975,17 +900,17 @@ __global__ __launch_bounds__(kBlock, 1) void k_prefix_deepen16(
 // Last H levels of the full-domain expansion depth-first (as k_prefix_build16's tail): one
 // lane per node at level nlev - H expands its subtree with a register stack of pending right
 // children (one 9-word slot per depth above the bottom), so the node state in registers grows
-// with H, not 2^H as in k_fd_tail16, and H = 4..5 fits.  Leaf-parent i (bits Msb-first = the
+// with H, not with 2^H as under a breadth-first tail, and H = 4..5 fits.  Leaf-parent i (bits Msb-first = the
 // choices at depths 0 .. H-2) resumes from the slot at the depth of i's lowest set bit; its
 // expansion writes y for leaves 2i, 2i + 1 of the node's 2^H contiguous outputs.
-// ROWS: the nodes of level lev0 are PrefixTable rows (k_prefix_build16's output: s with t in bit 0
-// of byte 15, then v) at s_in; v_in / t_in unused.
-template <int H, bool ROWS = false>
+// The nodes of level lev0 are PrefixTable rows (k_prefix_build16's output: s with t in bit 0 of
+// byte 15, then v).
+template <int H>
 __global__ __launch_bounds__(kBlock, 1) void k_fd_dfs16(
     const uint32_t* __restrict__ tab, const RoundKeys rk, const uint4* __restrict__ cw_s,
     const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const uint4* __restrict__ cw_np1,
-    const uint32_t lev0, const uint64_t nnodes, const uint4* __restrict__ s_in, const uint4* __restrict__ v_in,
-    const uint8_t* __restrict__ t_in, uint4* __restrict__ ys, uint32_t* __restrict__ ctr) {
+    const uint32_t lev0, const uint64_t nnodes, const uint4* __restrict__ rows, uint4* __restrict__ ys,
+    uint32_t* __restrict__ ctr) {
   static_assert(H >= 2 && H <= 6, "depth-first tail of 2..6 levels");
   __shared__ uint32_t lds[kLdsWords];
   lds_fill_tables(lds, tab);
@@ -999,16 +924,11 @@ __global__ __launch_bounds__(kBlock, 1) void k_fd_dfs16(
     const uint64_t jj = live ? j : nnodes - 1;
     uint32_t stk[H - 1][9];  // pending right children: s[4] | v[4] | t, by depth
     uint32_t n[9];
-    if (ROWS) {
-      const uint4 sv = s_in[2 * jj], vv = s_in[2 * jj + 1];
+    {
+      const uint4 sv = rows[2 * jj], vv = rows[2 * jj + 1];
       n[0] = sv.x; n[1] = sv.y; n[2] = sv.z; n[3] = sv.w & kMaskLast;
       n[4] = vv.x; n[5] = vv.y; n[6] = vv.z; n[7] = vv.w;
       n[8] = (sv.w >> 24) & 1u;
-    } else {
-      const uint4 sv = s_in[jj], vv = v_in[jj];
-      n[0] = sv.x; n[1] = sv.y; n[2] = sv.z; n[3] = sv.w;
-      n[4] = vv.x; n[5] = vv.y; n[6] = vv.z; n[7] = vv.w;
-      n[8] = t_in[jj];
     }
     uint4* y = ys + (jj << H);
     for (uint32_t i = 0; i < (1u << (H - 1)); ++i) {
@@ -1057,26 +977,6 @@ __global__ __launch_bounds__(kBlock, 1) void k_fd_dfs16(
       }
     }
   }
-}
-
-// Root node for full-domain eval: s = s0 (k.s0s[0]), v = 0, t = party.
-__global__ void k_fd_root16(const uint4* __restrict__ s0, const uint32_t party, uint4* __restrict__ s,
-                            uint4* __restrict__ v, uint8_t* __restrict__ t) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    s[0] = s0[0];
-    v[0] = make_uint4(0u, 0u, 0u, 0u);
-    t[0] = (uint8_t)party;
-  }
-}
-
-// All 2^n points of an n-bit domain as big-endian N-byte strings (LAMBDA >= 32 full domain).
-__global__ void k_domain_points(const uint32_t nbytes, const uint64_t count, uint8_t* __restrict__ xs) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count;
-       i += (uint64_t)gridDim.x * blockDim.x)
-    for (uint32_t b = 0; b < nbytes; ++b) {
-      const uint32_t sh = 8u * (nbytes - 1u - b);
-      xs[i * nbytes + b] = sh < 64 ? (uint8_t)(i >> sh) : 0u;
-    }
 }
 
 }  // namespace

@@ -240,7 +240,9 @@ __global__ __launch_bounds__(kBlock, 1) void k_prg16_mmo(const uint32_t* __restr
   }
 }
 
-// Full-domain level with the MMO PRG: one lane per parent, four blocks give both children.
+// Full-domain level with the MMO PRG (dcf_eval_full_domain_device's MMO branch alone): one lane per
+// parent, four blocks give both children.  Node state (s, v, t) lives in SoA buffers indexed by the
+// big-endian x prefix, 33 bytes per node; the last level writes y.
 __global__ __launch_bounds__(kBlock, 1) void k_fd_level16_mmo(
     const uint32_t* __restrict__ tab, const uint4* __restrict__ rk128, const uint4* __restrict__ cw_s,
     const uint4* __restrict__ cw_v, const uint8_t* __restrict__ cw_t, const uint4* __restrict__ cw_np1,
@@ -293,6 +295,17 @@ __global__ __launch_bounds__(kBlock, 1) void k_fd_level16_mmo(
       t_out[2 * j] = (uint8_t)tl;
       t_out[2 * j + 1] = (uint8_t)tr;
     }
+  }
+}
+
+// Root node of the MMO full-domain levels (k_fd_level16_mmo's SoA buffers): s = s0 (k.s0s[0]), v = 0,
+// t = party.
+__global__ void k_fd_root16(const uint4* __restrict__ s0, const uint32_t party, uint4* __restrict__ s,
+                            uint4* __restrict__ v, uint8_t* __restrict__ t) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    s[0] = s0[0];
+    v[0] = make_uint4(0u, 0u, 0u, 0u);
+    t[0] = (uint8_t)party;
   }
 }
 

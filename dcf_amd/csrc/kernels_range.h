@@ -14,11 +14,13 @@
 //                     prefix + root index.  h = 0 (LEAF): the "roots" are the points themselves and
 //                     the kernel writes y (small counts).
 //   k_range_level16   the h - kFdTail levels below the roots, breadth-first over all blocks at
-//                     once, one launch per level (as k_fd_level16, on 32-byte rows): the nodes of
-//                     all blocks stay consecutive, in leaf order, in two ping-pong buffers.
-//   k_range_tail16    the register depth-first tail of k_fd_dfs16 on those nodes; a
-//                     leaf's output index is its distance from x0 and leaves outside the range are
-//                     not stored.
+//                     once, one launch per level, on 32-byte PrefixTable rows: the nodes of
+//                     all blocks stay consecutive, in leaf order, in two ping-pong buffers.  The
+//                     child rules are fd_children's (kernels16.h) or mmo_children's.  The MMO
+//                     prefix-table build (build_prefix) is this kernel from level 1 down.
+//   k_range_tail16    the register depth-first tail of k_fd_dfs16 (the full-domain fast path's,
+//                     kernels16.h) on those nodes; a leaf's output index is its distance from x0
+//                     and leaves outside the range are not stored.
 // Each is a template on the key policy, RangeOneKey or RangeKeys, and is instantiated for both.
 // k_range_tail16 is also a template on the output policy: RangeStore writes every leaf inside the
 // range, RangeFold XORs the leaves, each masked by its row of a public table, into one LAMBDA-byte
@@ -188,7 +190,7 @@ struct RangeHirose {
   static __device__ __forceinline__ void children(A&&... a) { fd_children(a...); }
 };
 
-// Interior, one launch per level (k_fd_level16 on PrefixTable-style rows): the parents of level
+// Interior, one launch per level, on PrefixTable-style rows: the parents of level
 // `lev` — rows in[2j], in[2j + 1] of all blocks of all keys, consecutive in leaf order — become the
 // children rows out[4j .. 4j + 3], one lane per parent, waves claiming units of parents from
 // ctr[0].  blocks: the call's AES block count, PRG::kBlocks per parent.
@@ -405,7 +407,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_range_tail16(
   if ((threadIdx.x & 63u) == 0 && nlive) atomicAdd(blocks, PRG::kBlocks * ((1u << H) - 1u) * nlive);
 }
 
-// Points x0 + i, i in [0, count), as N-byte big-endian strings (a sibling of k_domain_points): the
+// Points x0 + i, i in [0, count), as N-byte big-endian strings: the
 // add carries across all 16 low bytes; bytes above them come from `top` (the host splits a range
 // at the one place where the low 128 bits wrap).
 __global__ void k_range_points(const uint32_t nbytes, const RangeX x0, const RangeTop top, const uint64_t count,

@@ -23,8 +23,9 @@
 
 namespace {
 
-// Both children of (s, v, t) under the correction words of their level (lib.rs:176-189 with x bit
-// 0 and 1, as k_fd_level16_mmo): four blocks.
+// Both children of (s, v, t) under the correction words of their level: four blocks, o = s_L, v_L,
+// s_R, v_R of mmo_prg4 (already masked), then lib.rs:176-189 with x bit 0 and 1 and tm = t ? ~0 : 0:
+//   s_l = o[0] ^ tm & cw_s    v_l = v ^ o[1] ^ tm & cw_v    t_l = t_L ^ t & cw_tl   (_r: o[2], o[3], t_R, cw_tr)
 __device__ __forceinline__ void mmo_children(const uint32_t* lds, uint32_t lc, const uint4* rks,
                                              const uint32_t (&csw)[4], const uint32_t (&cvw)[4], uint32_t ct,
                                              const uint32_t (&s)[4], const uint32_t (&v)[4], uint32_t t,

@@ -132,8 +132,8 @@ int dcf_prg_set_eval_mode(dcf_prg* prg, int mode);
  * stream head (bytes [0,32) of the walk and the t-vector rows, 80 B per node).
  * Every point's walk (lib.rs:174-189) passes through the node of the key's GGM
  * tree named by its first D bits, and that node's (s, v, t) depends on nothing
- * else, so eval expands the top D levels once (2^(D+1) AES blocks, 33 B per node,
- * as the full-domain eval does) and starts each point at level D from its node:
+ * else, so eval expands the top D levels once (2^(D+1) AES blocks, 32 B per node)
+ * and starts each point at level D from its node:
  * D fewer levels per point, identical output bytes.
  *   levels = -1: automatic (the default): D = log2(points) (Aes128MatyasMeyerOseasPrg:
  *                log2(points) - 1), at most 27 (LAMBDA >= 32: log2(points) - 1, at most
@@ -149,8 +149,9 @@ int dcf_prg_set_eval_mode(dcf_prg* prg, int mode);
  *                         2 * 33 * 2^(D-H) with H = min(4, D - 18) levels built depth-first
  *                         (33 * 2^D when D <= 18) — 4.85e9 B at D = 27 (2^28 points, the auto
  *                         cap), 2.42e9 at 26, 0.61e9 at 24 (C2);
- *   MMO, LAMBDA = 16:     2 * 33 * 2^D (level-by-level build, rows packed into one half) —
- *                         8.86e9 B at D = 27;
+ *   MMO, LAMBDA = 16:     48 * 2^D (level-by-level build on rows: the table and the level above
+ *                         it) — 6.44e9 B at D = 27; dcf_prg_set_prefix_max_bytes still counts
+ *                         2 * 33 * 2^D, the build's earlier layout, so a cap picks the depth it picked;
  *   LAMBDA >= 32:         160 * 2^D (80-B rows + the build's two node buffers) — 0.34e9 at 21.
  * Multi-key stream eval (LAMBDA = 16, >= 32 points per key, 8N > 6 levels):
  * each key's own top tree of depth 5 (32 rows of 32 B per key, 36 PRG calls per key)
@@ -325,8 +326,10 @@ int dcf_share_from_bincode(size_t n_bytes, size_t lambda, const uint8_t* in, siz
 /* Full-domain eval: ys[x] = Dcf::eval(party, k, x) for every x in
  * [0, 2^(8N)), x read big-endian (Msb0, lib.rs:181) — i.e. the output of
  * dcf_eval_device over all points in increasing order.  ys: 2^(8N) * lambda
- * bytes.  At lambda = 16 the tree is expanded breadth-first (2 AES blocks per
- * leaf instead of 16N per point); N <= 4. */
+ * bytes.  The key's tree is expanded once (lambda = 16: 2 AES blocks per leaf
+ * instead of 16N per point), by a path of its own for lambda = 16 (Hirose from N = 2,
+ * Aes128MatyasMeyerOseasPrg) and otherwise as dcf_eval_range_device over x0 = 0,
+ * count = 2^(8N), whose block count it then reports; N <= 4. */
 int dcf_eval_full_domain_device(dcf_prg* prg, size_t n_bytes, int party, const uint8_t* cwb, const uint8_t* s0,
                                 uint8_t* ys, void* stream);
 

@@ -2,9 +2,9 @@
 
 A dcf_prg leases its workspaces from a LIFO pool, so a single caller gets the same workspace back
 for every call, with the buffers of all earlier calls already grown and still holding their bytes:
-the shared-prefix table / per-key top trees / MMO halves in d_pfx, the LAMBDA >= 32, full-domain and
-range layouts in d_ws, the work counter and block count in d_ctr, the grow-only digests, the staging
-buffers.  The other GPU tests build a fresh prg per case; these keep one and change the path, the
+the shared-prefix table / per-key top trees / MMO level rows in d_pfx, the LAMBDA >= 32, range and
+MMO full-domain layouts in d_ws (full-domain eval lays out a range call's, but for its two own
+paths), the work counter and block count in d_ctr, the grow-only digests, the staging buffers.  The other GPU tests build a fresh prg per case; these keep one and change the path, the
 depth, the size and the stream from call to call, so state that leaks from call k into call k + 1
 shows as wrong bytes, a written guard row or a wrong block count.
 
@@ -53,7 +53,8 @@ STEP_BUFFERS = {
     "eval_device": frozenset({"d_ctr", "d_pfx", "d_ws", "d_dig", "d_tctr"}),
     "eval_multikey": frozenset({"d_ctr", "d_pfx", "d_kdig", "d_ws", "d_dig", "d_tctr"}),
     "gen_batch": frozenset({"d_ws"}),
-    "full_domain": frozenset({"d_ctr", "d_pfx", "d_ws", "d_dig"}),
+    # the fast path's table, the MMO levels' nodes, else a range call's
+    "full_domain": frozenset({"d_ctr", "d_pfx", "d_ws", "d_dig", "d_tctr"}),
     "range_device": frozenset({"d_ctr", "d_ws", "d_dig", "d_tctr"}),
     "range_host": frozenset({"d_ctr", "d_ws", "d_dig", "d_tctr", "stage"}),
     "range_multikey": frozenset({"d_ctr", "d_ws"}),
@@ -212,8 +213,8 @@ def pfx_ladder_hirose16(nb):
 
 
 def pfx_ladder_mmo16(nb):
-    """d_pfx under the MMO PRG (two halves, level-by-level build).  The library caps a forced depth at
-    28 for either PRG (kPrefixMaxForced, as prefix_depth() below) and at 8N - 1; tests/test_mmo.py
+    """d_pfx under the MMO PRG (the table and the rows of the level above it, level-by-level build).
+    The library caps a forced depth at 28 for either PRG (kPrefixMaxForced, as prefix_depth() below) and at 8N - 1; tests/test_mmo.py
     goes up to 24; 23 is the deepest here (0.55 GB)."""
     return (_depth(1, nb) + _depth(15, nb) + _depth(23, nb) + [S("eval_multikey", nb=nb, K=200, P=32)] + _depth(8, nb) +
             [S("trim")] + _depth(15, nb))
@@ -321,10 +322,22 @@ def prefix_depth(config, st, step):
     return min(d, cap) if d >= 8 else 0
 
 
+def fd_route(config, step):
+    """The path of a full_domain step: "fast" (Hirose, LAMBDA = 16, the table build's 8N - 4 levels at
+    least 12), "levels" (MMO, LAMBDA = 16: a launch per level between two node buffers in d_ws), else
+    "range": a range_device step over the whole domain."""
+    kind, lam, _ = CONFIGS[config]
+    if lam == 16 and kind == "mmo":
+        return "levels"
+    return "fast" if lam == 16 and 8 * step.get("nb") - 4 >= 12 else "range"
+
+
 def extent(config, st, step, buffer):
     """Bytes (to the leading term) a step lays out in `buffer`; None when it does not use it."""
     kind, lam, _ = CONFIGS[config]
     k, nb = step.kind, step.get("nb")
+    if k == "full_domain" and fd_route(config, step) == "range":
+        return extent(config, st, S("range_device", nb=nb, count=1 << (8 * nb)), buffer)
     if buffer not in STEP_BUFFERS[k] or k == "trim":
         return None
     if buffer == "d_pfx":
@@ -336,12 +349,12 @@ def extent(config, st, step, buffer):
             return step.get("K") * 1024 if trees else None
         if k == "eval_multikey" and lam > 16 and kind == "hirose" and st.levels > 0:  # key by key, a table each
             return 80 << min(st.levels, 30, 8 * nb - 1)
-        if k == "full_domain" and lam == 16 and kind == "hirose" and 8 * nb - 4 >= 12:
+        if k == "full_domain" and fd_route(config, step) == "fast":
             return 32 << (8 * nb - 4)
         return None
     if buffer == "d_ws":
-        if k == "full_domain":
-            return 2 * 33 * (1 << (8 * nb)) if lam == 16 and 8 * nb - 4 < 12 else (64 << (8 * nb) if lam > 16 else None)
+        if k == "full_domain":  # the fast path lays out its table alone
+            return 2 * 33 * (1 << (8 * nb)) if fd_route(config, step) == "levels" else None
         if k in ("range_device", "range_host", "range_multikey"):
             return step.get("count") * step.get("K", 1) * (4 if lam == 16 else 64 + 20)
         if lam > 16 and k in ("host_eval", "eval_device"):
@@ -676,7 +689,9 @@ def step_full_domain(ctx, rng, step):
             assert bad.size == 0, what + ("party", b, "first mismatching x", rows[bad[:8]])
             ys.append(y)
         assert _range_rec(ys[0] ^ ys[1], beta, int.from_bytes(alpha, "big"), count, bound), ("reconstruction",) + what
-    return Pending(check)
+    # full-domain eval's own paths document no count; every other shape is a range call over [0, count)
+    blocks = _range_blocks(ctx, nb, 1, 0, count, d.range_subtree_levels(count)) if fd_route(ctx.config, step) == "range" else None
+    return Pending(check, blocks)
 
 
 def _unaligned_x0(rng, nb):

@@ -548,10 +548,12 @@ def test_error_codes_on_device(dcf):
     assert e.value.code == -2
 
 
-@pytest.mark.parametrize("nb,lam", [(1, 16), (2, 16), (3, 16), (1, 32), (1, 64)])
+@pytest.mark.parametrize("nb,lam", [(1, 16), (2, 16), (3, 16), (1, 32), (1, 64), (2, 32), (1, 48)])
 def test_full_domain_eval_vs_oracle(dcf, nb, lam):
-    """Full-domain eval (tree expansion) == pointwise oracle eval over every x.  N = 2 and 3 take
-    the one-launch table build for the levels above the depth-first tail (D = 12 and 20)."""
+    """Full-domain eval (tree expansion) == pointwise oracle eval over every x.  At LAMBDA = 16 N = 2
+    and 3 take the one-launch table build for the levels above the depth-first tail (D = 12 and
+    20); every other shape is the range [0, 2^(8N)) through the range driver: N = 1 its root walk
+    (h = 0), (2, 32) the LAMBDA >= 32 tree engine with h = 8, (1, 48) and (1, 64) its t-vector tail."""
     import torch
     rng = np.random.default_rng(nb * 100 + lam)
     keys = [rng.bytes(32) for _ in range(2 if lam == 16 else 18)]

@@ -179,22 +179,28 @@ def test_gpu_mmo_batch_gen_multikey_eval(dcf, K, P):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("nb", [1, 2])
-def test_gpu_mmo_full_domain(dcf, nb):
+@pytest.mark.parametrize("nb,lam", [pytest.param(1, 16, id="1"), pytest.param(2, 16, id="2"), pytest.param(1, 32, id="1-lam32")])
+def test_gpu_mmo_full_domain(dcf, nb, lam):
+    """LAMBDA = 16: the MMO level launches of full-domain eval.  LAMBDA = 32: the whole domain as a range
+    call, whose points are materialised and run through eval."""
     import torch
-    rng = np.random.default_rng(900 + nb)
-    keys = [rng.bytes(16) for _ in range(4)]
-    prg, P = dcf.Aes128MatyasMeyerOseasPrg(keys, 16), O.OracleMmoPrg(keys, 16)
-    d = dcf.DcfImpl(nb, 16, prg)
-    alpha, beta, s0, s1 = rng.bytes(nb), rng.bytes(16), rng.bytes(16), rng.bytes(16)
+    rng = np.random.default_rng(900 + nb + lam - 16)
+    keys = [rng.bytes(16) for _ in range(4 * lam // 16)]
+    prg, P = dcf.Aes128MatyasMeyerOseasPrg(keys, lam), O.OracleMmoPrg(keys, lam)
+    d = dcf.DcfImpl(nb, lam, prg)
+    alpha, beta, s0, s1 = rng.bytes(nb), rng.bytes(lam), rng.bytes(lam), rng.bytes(lam)
     ok = O.gen(P, alpha, beta, s0, s1, 0)
     k = d.gen(dcf.CmpFn(alpha, beta), [s0, s1], dcf.BoundState.LtBeta)
-    cwb = torch.from_numpy(np.frombuffer(dcf.share_to_cwb(k, nb, 16), np.uint8).copy()).cuda()
+    cwb = torch.from_numpy(np.frombuffer(dcf.share_to_cwb(k, nb, lam), np.uint8).copy()).cuda()
     xs = np.array([list(i.to_bytes(nb, "big")) for i in range(1 << (8 * nb))], np.uint8)
+    ys = []
     for b, s in ((0, s0), (1, s1)):
         y = d.eval_full_domain_device(bool(b), cwb, torch.from_numpy(np.frombuffer(s, np.uint8).copy()).cuda())
         torch.cuda.synchronize()
-        assert np.array_equal(y.cpu().numpy(), O.eval_(P, b, ok, s, xs, nthreads=8)), (nb, b)
+        ys.append(y.cpu().numpy())
+        assert np.array_equal(ys[b], O.eval_(P, b, ok, s, xs, nthreads=8)), (nb, lam, b)
+    a, rec = int.from_bytes(alpha, "big"), ys[0] ^ ys[1]
+    assert not rec[a:].any() and (rec[:a] == np.frombuffer(beta, np.uint8)).all()
 
 
 @pytest.mark.gpu

@@ -13,6 +13,8 @@ from .dcf import (  # noqa: F401
     CmpFn,
     Cw,
     DcfImpl,
+    Engine,
+    EvalPlan,
     MultiGpuDcf,
     Share,
     cwb_bytes,
@@ -23,6 +25,6 @@ from .dcf import (  # noqa: F401
 )
 
 __all__ = [
-    "Aes128MatyasMeyerOseasPrg", "Aes256HirosePrg", "BoundState", "CmpFn", "Cw", "DcfImpl", "MultiGpuDcf", "Share", "point_slice", "DcfError",
+    "Aes128MatyasMeyerOseasPrg", "Aes256HirosePrg", "BoundState", "CmpFn", "Cw", "DcfImpl", "Engine", "EvalPlan", "MultiGpuDcf", "Share", "point_slice", "DcfError",
     "cwb_bytes", "cwb_np1_offset", "cwb_to_share", "share_to_cwb", "load", "LIB_PATH",
 ]

@@ -1365,6 +1365,34 @@ int dcf_eval_prefix_levels(const dcf_prg* p, size_t n_bytes, size_t num_keys, si
   return (int)plan_eval(p, snapshot(p), n_bytes, num_keys, points_per_key).depth;
 }
 
+// The public image of Engine (include/dcf_hip.h); no default: a new Engine value fails to compile here.
+static int public_engine(Engine e) {
+  switch (e) {
+    case Engine::WideBatch: return DCF_ENGINE_WIDE_BATCH;
+    case Engine::WidePerKey: return DCF_ENGINE_WIDE_PER_KEY;
+    case Engine::Mmo16: return DCF_ENGINE_MMO16;
+    case Engine::Row2: return DCF_ENGINE_ROW2;
+    case Engine::Row: return DCF_ENGINE_ROW;
+    case Engine::Oct: return DCF_ENGINE_OCT;
+    case Engine::Pair: return DCF_ENGINE_PAIR;
+    case Engine::Stream: return DCF_ENGINE_STREAM;
+    case Engine::TTable: return DCF_ENGINE_TTABLE;
+  }
+  return -1;
+}
+
+int dcf_eval_plan(const dcf_prg* p, size_t n_bytes, size_t num_keys, size_t points_per_key, int* engine,
+                  int* key_mode, int* prefix_levels, int* small) {
+  if (!p) return fail(DCF_ERR_ARG, "null prg");
+  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
+  const EvalPlan pl = plan_eval(p, snapshot(p), n_bytes, num_keys, points_per_key);
+  if (engine) *engine = public_engine(pl.engine);
+  if (key_mode) *key_mode = pl.key_mode;
+  if (prefix_levels) *prefix_levels = (int)pl.depth;
+  if (small) *small = pl.small ? 1 : 0;
+  return pl.unsupported ? fail(DCF_ERR_UNSUPPORTED, pl.unsupported) : DCF_OK;
+}
+
 int dcf_prg_set_prefix_max_bytes(dcf_prg* p, size_t max_bytes) {
   if (!p) return fail(DCF_ERR_ARG, "null prg");
   p->prefix_cap = max_bytes;

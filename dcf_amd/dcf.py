@@ -28,7 +28,7 @@ from __future__ import annotations
 import ctypes
 import enum
 from dataclasses import dataclass, field
-from typing import List, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -40,6 +40,29 @@ class BoundState(enum.IntEnum):
     """lib.rs:342-349."""
     LtBeta = 0  # f(x) = beta iff x < alpha
     GtBeta = 1  # f(x) = beta iff x > alpha
+
+
+class Engine(enum.IntEnum):
+    """`dcf_engine` of include/dcf_hip.h: the kernel family an eval call runs."""
+    WIDE_BATCH = 0
+    WIDE_PER_KEY = 1
+    MMO16 = 2
+    ROW2 = 3
+    ROW = 4
+    OCT = 5
+    PAIR = 6
+    STREAM = 7
+    TTABLE = 8
+
+
+class EvalPlan(NamedTuple):
+    """`dcf_eval_plan`: what an eval call of a shape decides before it launches anything.
+    unsupported: None, or why the eval call itself fails with DCF_ERR_UNSUPPORTED."""
+    engine: Engine
+    key_mode: int
+    prefix_levels: int
+    small: bool
+    unsupported: Optional[str] = None
 
 
 @dataclass
@@ -196,6 +219,21 @@ class Aes256HirosePrg:
         if r < 0:
             check(r)
         return r
+
+    def eval_plan(self, n_bytes: int, num_keys: int, points_per_key: int) -> EvalPlan:
+        """The engine, key mode, prefix depth and small-batch flag an eval of this shape uses under
+        the prg's current settings (dcf_eval_plan; nothing is launched).  A shape the eval call
+        rejects comes back with `unsupported` set to the reason; other errors raise."""
+        L = _lib.load()
+        e, k, d, s = ctypes.c_int(-1), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        rc = L.dcf_eval_plan(self._h, int(n_bytes), int(num_keys), int(points_per_key), ctypes.byref(e),
+                             ctypes.byref(k), ctypes.byref(d), ctypes.byref(s))
+        why = None
+        if rc == -7:  # DCF_ERR_UNSUPPORTED: the outputs are filled
+            why = L.dcf_last_error().decode(errors="replace")
+        else:
+            check(rc)
+        return EvalPlan(Engine(e.value), int(k.value), int(d.value), bool(s.value), why)
 
     @staticmethod
     def prefix_deepen_calls(depth: int, points: int) -> int:

@@ -239,6 +239,21 @@ class DcfImpl final : public Dcf<N, LAMBDA> {
     check(dcf_eval_range_device(prg_.handle(), N, b ? 1 : 0, cwb, s0, x0.data(), count, ys, stream));
   }
 
+  // What an eval of num_keys x points_per_key points on `prg` decides before it launches anything
+  // (dcf_eval_plan).  `unsupported` is empty, or why the eval call itself returns DCF_ERR_UNSUPPORTED.
+  struct EvalPlan {
+    dcf_engine engine;
+    int key_mode, prefix_levels;
+    bool small;
+    std::string unsupported;
+  };
+  static EvalPlan eval_plan(const PrgT& prg, size_t num_keys, size_t points_per_key) {
+    int e = 0, k = 0, d = 0, s = 0;
+    const int rc = dcf_eval_plan(prg.handle(), N, num_keys, points_per_key, &e, &k, &d, &s);
+    if (rc != DCF_OK && rc != DCF_ERR_UNSUPPORTED) check(rc);
+    return EvalPlan{(dcf_engine)e, k, d, s != 0, rc == DCF_OK ? std::string() : std::string(dcf_last_error())};
+  }
+
   // Height of the aligned blocks eval_range expands for `count` points.
   static int range_subtree_levels(uint64_t count) { return dcf_eval_range_subtree_levels(N, count); }
   // Outputs per launch group of the Hirose LAMBDA >= 32 tree path of eval_range (0: not that path).

@@ -159,6 +159,41 @@ int dcf_prg_set_eval_mode(dcf_prg* prg, int mode);
 int dcf_prg_set_prefix_levels(dcf_prg* prg, int levels);
 /* The prefix depth D a dcf_eval* call of this shape would use (0 = none). */
 int dcf_eval_prefix_levels(const dcf_prg* prg, size_t n_bytes, size_t num_keys, size_t points_per_key);
+
+/* The kernel family an eval call runs (dcf_eval_plan). */
+typedef enum dcf_engine {
+  DCF_ENGINE_WIDE_BATCH = 0,   /* LAMBDA >= 32, Hirose: several keys per pass of the stream head */
+  DCF_ENGINE_WIDE_PER_KEY = 1, /* LAMBDA >= 32: the stream head (Hirose) or the MMO walk, key by key */
+  DCF_ENGINE_MMO16 = 2,        /* Aes128MatyasMeyerOseasPrg at LAMBDA = 16, whatever the engine setting */
+  DCF_ENGINE_ROW2 = 3,         /* latency kernels, one key in automatic mode: up to 2048 points, */
+  DCF_ENGINE_ROW = 4,          /*   up to 8192, */
+  DCF_ENGINE_OCT = 5,          /*   up to 32768 */
+  DCF_ENGINE_PAIR = 6,         /* lockstep walk on a lane pair per point (small batches, automatic mode) */
+  DCF_ENGINE_STREAM = 7,       /* DCF_EVAL_STREAM's engine */
+  DCF_ENGINE_TTABLE = 8        /* DCF_EVAL_TTABLE's engine */
+} dcf_engine;
+/* The plan of a dcf_eval* call of this shape under the prg's current settings: what
+ * dcf_eval_device (num_keys = 1, points_per_key = m), dcf_eval_multikey_device and the host entry
+ * points decide before they launch anything.  Pure arithmetic on the prg's configuration and its
+ * device's compute-unit count; nothing is launched.  Any of the four outputs may be NULL.
+ *   engine         a dcf_engine.  LAMBDA >= 32: WIDE_BATCH for 2 or more keys of at most 32768
+ *                  points each with the Hirose PRG and no forced prefix depth, else WIDE_PER_KEY.
+ *                  LAMBDA = 16: MMO16 for that PRG; Hirose in automatic mode with one key, N <= 32
+ *                  and no forced depth: ROW2 up to 2048 points, ROW up to 8192, OCT up to 32768;
+ *                  otherwise PAIR while `small`; otherwise STREAM (DCF_EVAL_STREAM, or automatic
+ *                  mode with one key or N <= 32) or TTABLE (DCF_EVAL_TTABLE, or automatic mode with
+ *                  several keys at N > 32).
+ *   key_mode       how a lockstep kernel finds a point's key: 0 one key, 1 points_per_key % 64 == 0
+ *                  (a wave holds one key), 2 any other points_per_key.
+ *   prefix_levels  what dcf_eval_prefix_levels returns for the shape.
+ *   small          1 at LAMBDA = 16 in automatic mode when the call has fewer points than two per
+ *                  lane of the device (num_keys * points_per_key < 2 * compute units * 1024).
+ * Returns DCF_OK, or DCF_ERR_UNSUPPORTED where the eval call itself would fail before any device
+ * work (multi-key stream eval at N > 32 or with 2^31 or more points per key; more than 2^32 64-point
+ * units on the T-table engine): dcf_last_error carries the reason and the outputs are still filled.
+ * null prg -> DCF_ERR_ARG, n_bytes == 0 -> DCF_ERR_N (outputs untouched). */
+int dcf_eval_plan(const dcf_prg* prg, size_t n_bytes, size_t num_keys, size_t points_per_key, int* engine,
+                  int* key_mode, int* prefix_levels, int* small);
 /* Keys per kernel launch of a LAMBDA = 16 multi-key stream eval (dcf_eval_multikey_device and
  * the host entry points with several keys): min(2^24, 2^31 / points_per_key, 2^30 / 8N), at
  * least 1 — the engine's point, work and CW-digest-row indices are 32-bit, so a larger call runs

@@ -18,6 +18,17 @@ pub const DCF_ERR_HIP: c_int = -6;
 pub const DCF_ERR_UNSUPPORTED: c_int = -7;
 pub const DCF_ERR_KEY: c_int = -8;
 
+/// `dcf_engine` of include/dcf_hip.h (the `engine` output of `dcf_eval_plan`).
+pub const DCF_ENGINE_WIDE_BATCH: c_int = 0;
+pub const DCF_ENGINE_WIDE_PER_KEY: c_int = 1;
+pub const DCF_ENGINE_MMO16: c_int = 2;
+pub const DCF_ENGINE_ROW2: c_int = 3;
+pub const DCF_ENGINE_ROW: c_int = 4;
+pub const DCF_ENGINE_OCT: c_int = 5;
+pub const DCF_ENGINE_PAIR: c_int = 6;
+pub const DCF_ENGINE_STREAM: c_int = 7;
+pub const DCF_ENGINE_TTABLE: c_int = 8;
+
 extern "C" {
     pub fn dcf_version() -> *const c_char;
     pub fn dcf_last_error() -> *const c_char;
@@ -31,6 +42,9 @@ extern "C" {
     pub fn dcf_prg_set_eval_mode(prg: *mut DcfPrg, mode: c_int) -> c_int;
     pub fn dcf_prg_set_prefix_levels(prg: *mut DcfPrg, levels: c_int) -> c_int;
     pub fn dcf_eval_prefix_levels(prg: *const DcfPrg, n_bytes: usize, num_keys: usize, points_per_key: usize) -> c_int;
+    pub fn dcf_eval_plan(prg: *const DcfPrg, n_bytes: usize, num_keys: usize, points_per_key: usize,
+                         engine: *mut c_int, key_mode: *mut c_int, prefix_levels: *mut c_int,
+                         small: *mut c_int) -> c_int;
     pub fn dcf_eval_keys_per_launch(n_bytes: usize, points_per_key: usize) -> usize;
     pub fn dcf_prg_set_prefix_max_bytes(prg: *mut DcfPrg, max_bytes: usize) -> c_int;
     pub fn dcf_prefix_deepen_calls(depth: c_int, points: usize) -> u64;

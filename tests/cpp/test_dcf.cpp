@@ -134,6 +134,14 @@ int main() {
     }
     CHECK(threw);
   }
+  {  // dcf_eval_plan: one point of one key runs the smallest latency kernel; 5 x 33 points the pair walk
+    const auto one = Dcf16::eval_plan(prg, 1, 1);
+    CHECK(one.engine == DCF_ENGINE_ROW2 && one.key_mode == 0 && one.small && one.unsupported.empty());
+    CHECK(one.prefix_levels == dcf_eval_prefix_levels(prg.handle(), 16, 1, 1));
+    const auto mk = Dcf16::eval_plan(prg, 5, 33);
+    CHECK(mk.engine == DCF_ENGINE_PAIR && mk.key_mode == 2);
+    CHECK((dcf::DcfImpl<16, 16, decltype(mmo)>::eval_plan(mmo, 5, 64).engine == DCF_ENGINE_MMO16));
+  }
   std::printf("%s (%d failures)\n", failures ? "FAILED" : "cpp mirror ok", failures);
   return failures ? 1 : 0;
 }

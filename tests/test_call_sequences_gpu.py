@@ -525,6 +525,21 @@ def _stream_bounds(n, depth, points, trees=0):
     return trees + (n - depth) * points // 2, trees + 2 * (n - depth) * points
 
 
+def _assert_plan(ctx, step, nb, K, ppk):
+    """dcf_eval_plan names the engine the rule above predicts for this eval step (the rule stays:
+    it predicts the buffers), the key mode of the shape, and dcf_eval_prefix_levels' depth."""
+    E = ctx.dcf.Engine
+    total = K * ppk
+    want = {"wide": (E.WIDE_BATCH, E.WIDE_PER_KEY), "mmo": (E.MMO16,), "pair": (E.PAIR,), "ttable": (E.TTABLE,),
+            "stream": (E.STREAM,), "lat": (E.ROW2 if total <= 2048 else E.ROW if total <= 8192 else E.OCT,)}
+    plan = ctx.prg.eval_plan(nb, K, ppk)
+    assert plan.engine in want[engine(ctx.config, ctx.st, step)], ("eval_plan", plan, engine(ctx.config, ctx.st, step))
+    assert plan.unsupported is None and plan.key_mode == (0 if K == 1 else 1 if ppk % 64 == 0 else 2), ("eval_plan", plan)
+    assert plan.prefix_levels == ctx.prg.eval_prefix_levels(nb, K, ppk), ("eval_plan", plan)
+    if CONFIGS[ctx.config][1] == 16 and CONFIGS[ctx.config][0] == "hirose":
+        assert plan.small == (ctx.st.mode == 0 and total < STREAM_MIN), ("eval_plan", plan)
+
+
 def _eval_blocks(ctx, step, nb, K, ppk):
     """What dcf_prg_last_eval_blocks must read after this eval step, as (lo, hi), or None."""
     e = engine(ctx.config, ctx.st, step)
@@ -582,6 +597,7 @@ def step_eval_device(ctx, rng, step):
     import torch
     nb, m, lam = step.get("nb"), step.get("m"), ctx.lam
     bound = int(rng.integers(0, 2))
+    _assert_plan(ctx, step, nb, 1, m)
     ok, alpha, beta, seeds = _key(ctx, rng, nb, bound)
     xs = _xs(rng, m, nb, alpha)
     xd, cwb, d = torch.from_numpy(xs).cuda(), _dev(_cwb(ok)), ctx.d(nb)
@@ -597,6 +613,7 @@ def step_eval_device(ctx, rng, step):
 def step_host_eval(ctx, rng, step):
     nb, m, lam = step.get("nb"), step.get("m"), ctx.lam
     bound = int(rng.integers(0, 2))
+    _assert_plan(ctx, step, nb, 1, m)
     ok, alpha, beta, seeds = _key(ctx, rng, nb, bound)
     xs = _xs(rng, m, nb, alpha)
     d, outs = ctx.d(nb), []
@@ -613,6 +630,7 @@ def step_host_eval(ctx, rng, step):
 def step_eval_multikey(ctx, rng, step):
     import torch
     nb, K, P, lam = step.get("nb"), step.get("K"), step.get("P"), ctx.lam
+    _assert_plan(ctx, step, nb, K, P)
     keys = [_key(ctx, rng, nb, 0) for _ in range(K)]
     xs = rng.integers(0, 256, size=(K * P, nb), dtype=np.uint8)
     xs[::P] = np.stack([np.frombuffer(k[1], np.uint8) for k in keys])

@@ -22,7 +22,7 @@ LAMS = [16, 16, 16, 32, 48, 64, 80, 96, 112, 128, 144, 256, 272, 384, 512, 1024]
 
 
 # Extended sweeps (one-off GPU runs; the default is the suite's fixed list): DCF_FUZZ_CASES /
-# DCF_FUZZ_MK_CASES cases from DCF_FUZZ_SEED / DCF_FUZZ_MK_SEED, and with DCF_FUZZ_BIG=1 also
+# DCF_FUZZ_MK_CASES / DCF_FUZZ_MK2_CASES cases from DCF_FUZZ_SEED / DCF_FUZZ_MK_SEED / DCF_FUZZ_MK2_SEED, and with DCF_FUZZ_BIG=1 also
 # λ = 16 batches on the pair-walk (40000 points) and stream (600000) engines.
 _ENV = os.environ.get
 
@@ -53,6 +53,27 @@ def _mk_cases(n=int(_ENV("DCF_FUZZ_MK_CASES", "24")), seed=int(_ENV("DCF_FUZZ_MK
         K = int(rng.integers(1, 300))
         P = int(rng.choice([1, 5, 31, 32, 33, 64, 100]))
         out.append((i, lam, nb, K, P))
+    return out
+
+
+def _mk_cases2(n=int(_ENV("DCF_FUZZ_MK2_CASES", "32")), seed=int(_ENV("DCF_FUZZ_MK2_SEED", "0xF1ED"), 0)):
+    """A second multi-key list (the first stays as it is): either PRG, both bounds, every engine
+    setting, K * P and N beyond the first list's, through the runner of
+    tests/test_multikey_dispatch_gpu.py.  The default seed is the one of 0xF0B0 .. 0xF23F whose 32
+    shapes spread over the most routes (Hirose LAMBDA = 16 on the stream engine with and without top
+    trees, the T-table and the pair walk under both key modes and bounds, MMO-16, both PRGs at
+    LAMBDA >= 32), counted from the drawn shapes alone."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(n):
+        mmo = bool(rng.random() < 0.4)
+        bound = int(rng.integers(0, 2))
+        mode = int(rng.choice([0, 1, 4]))
+        lam = int(rng.choice([16, 16, 32, 64, 128]))
+        nb = int(rng.integers(1, 41 if lam == 16 else 21))
+        K = int(rng.integers(1, 301))
+        P = int(rng.choice([1, 5, 31, 32, 33, 64, 100, 128]))
+        out.append((i, mmo, bound, mode, lam, nb, K, P))
     return out
 
 
@@ -148,3 +169,16 @@ def test_fuzz_multikey_vs_oracle(dcf, case):
     lt = np.stack([_lt(xs[k * P:(k + 1) * P], alpha[k]) for k in range(K)])
     want = np.where(lt.reshape(-1)[:, None], np.repeat(beta, P, 0), 0).astype(np.uint8)
     assert np.array_equal(y0h ^ y1h, want), "reconstruction"
+
+
+@pytest.mark.parametrize("case", _mk_cases2(),
+                         ids=lambda c: f"m{c[0]}-{'mmo' if c[1] else 'hirose'}-b{c[2]}-mode{c[3]}-lam{c[4]}-n{c[5]}-K{c[6]}-P{c[7]}")
+def test_fuzz_multikey2_vs_oracle(dcf, case):
+    """Sentinels, reconstruction on every row, the oracle on the sampled keys and their CWB
+    (run_case); the engine is whatever dcf_eval_plan names for the shape (printed).  An engine
+    setting the plan calls unsupported for the shape (DCF_EVAL_STREAM with several keys at N > 32)
+    is replaced by automatic mode."""
+    from tests.test_multikey_dispatch_gpu import Case, run_case
+    i, mmo, bound, mode, lam, nb, K, P = case
+    run_case(dcf, Case(f"fuzz-mk2-{i}", kind="mmo" if mmo else "hirose", lam=lam, nb=nb, K=K, P=P, mode=mode, bound=bound,
+                       engine=None), seed=[0x4EED, i])

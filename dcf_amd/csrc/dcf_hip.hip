@@ -26,6 +26,7 @@
 #include <optional>
 #include <thread>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -303,6 +304,36 @@ int ensure_ctr(Workspace* w) {
   if (!w->d_ctr) HIP_TRY(hipMalloc(&w->d_ctr, kCtrBytes));
   return DCF_OK;
 }
+
+// Where the parts of a K-key CWB lie (include/dcf_hip.h), the one fact every engine shares:
+//   cw_s[8N][K][LAMBDA] | cw_v[8N][K][LAMBDA] | cw_t[8N][K] | pad to 16 B | cw_np1[K][LAMBDA]
+// B: const uint8_t for a block that is read (KeyBlock), uint8_t for gen's cwb_out (KeyBlockOut).
+template <class B>
+struct KeyBlockT {
+  using U4 = std::conditional_t<std::is_const<B>::value, const uint4, uint4>;
+  B *cws, *cwv, *cwt, *np1;
+  uint32_t nlev, lam;
+  uint64_t K;
+  KeyBlockT(B* cwb, size_t n_bytes, size_t lambda, size_t num_keys)
+      : cws(cwb), cwv(cwb + 8 * n_bytes * num_keys * lambda), cwt(cwb + 2 * 8 * n_bytes * num_keys * lambda),
+        np1(cwb + dcf_cwb_np1_offset(n_bytes, lambda, num_keys)), nlev((uint32_t)(8 * n_bytes)),
+        lam((uint32_t)lambda), K(num_keys) {}
+  // LAMBDA = 16: a row is one uint4
+  U4* s4() const { return reinterpret_cast<U4*>(cws); }
+  U4* v4() const { return reinterpret_cast<U4*>(cwv); }
+  U4* np14() const { return reinterpret_cast<U4*>(np1); }
+  // The block from key k0 on, for the kernels that find key k's row of a level at [level * K + k].
+  KeyBlockT from(uint64_t k0) const {
+    KeyBlockT b = *this;
+    b.cws += k0 * lam;
+    b.cwv += k0 * lam;
+    b.cwt += k0;
+    b.np1 += k0 * lam;
+    return b;
+  }
+};
+using KeyBlock = KeyBlockT<const uint8_t>;
+using KeyBlockOut = KeyBlockT<uint8_t>;
 
 // Phase timing (dcf_prg_set_phase_timing): event i of the lease's workspace on its stream.
 void phase_mark(dcf_prg*, Lease& L, int i) {
@@ -680,9 +711,10 @@ int reserve_pfx(Workspace* w, size_t need, hipStream_t st, hipError_t* oom) {
 // then one k_range_level16 launch per level.
 // pst (reuse_prefix, Hirose only): the gated build, which runs only if the device state word says
 // that no table is valid; reuse_prefix sets the hints again afterwards.
-int build_prefix(dcf_prg* p, Workspace* w, int party, const uint4* cws, const uint4* cwv, const uint8_t* cwt,
-                 const uint4* np1, const uint8_t* s0, uint32_t levels, PrefixTable* out, hipStream_t st,
-                 const uint32_t* pst = nullptr) {
+int build_prefix(dcf_prg* p, Workspace* w, int party, const KeyBlock& kb, const uint8_t* s0, uint32_t levels,
+                 PrefixTable* out, hipStream_t st, const uint32_t* pst = nullptr) {
+  const uint4 *cws = kb.s4(), *cwv = kb.v4(), *np1 = kb.np14();
+  const uint8_t* cwt = kb.cwt;
   w->ph.valid = false;  // d_pfx changes hands
   // Hirose: [table 2^D x 32 B | 2 x 2^S regions of 2^(D-1-S) nodes]
   // MMO: [table | the rows of level D - 1 | kPfxCtrs work counters, one per level launch | a block count]
@@ -732,12 +764,11 @@ int build_prefix(dcf_prg* p, Workspace* w, int party, const uint4* cws, const ui
 // build_prefix at depth d; in auto mode (prefix_levels < 0) an allocation failure retries
 // two levels shallower, down to 8, and then evaluates without a table (same output bytes).
 // d = 0: no table.  The depth built goes to w->last_prefix.
-int try_prefix(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, int party, const uint4* cws, const uint4* cwv,
-               const uint8_t* cwt, const uint4* np1, const uint8_t* s0, uint32_t d, PrefixTable* out, hipStream_t st,
-               const uint32_t* pst = nullptr) {
+int try_prefix(dcf_prg* p, const Cfg& c, Workspace* w, int party, const KeyBlock& kb, const uint8_t* s0, uint32_t d,
+               PrefixTable* out, hipStream_t st, const uint32_t* pst = nullptr) {
   *out = PrefixTable{nullptr, 0u};
   while (d) {
-    const int rc = build_prefix(p, w, party, cws, cwv, cwt, np1, s0, d, out, st, pst);
+    const int rc = build_prefix(p, w, party, kb, s0, d, out, st, pst);
     if (rc == DCF_OK) w->last_prefix = out->levels;
     if (rc != kPrefixNoMem) return rc;
     if (c.prefix_levels >= 0) return fail(DCF_ERR_HIP, t_err);  // a forced depth must fit
@@ -785,9 +816,12 @@ void launch_commit(Workspace* w, hipStream_t st, uint32_t expect, uint32_t depth
 // The table of a dcf_eval_device call of `total` points whose one-call depth is d (prefix_depth).
 // *out: the table and the depth the host expects; the walk reads the real depth from w->d_pst.
 // out->levels = 0: no table could be allocated, the walk starts at the root.
-int reuse_prefix(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, int party, const uint8_t* cwb,
-                 const uint4* cws, const uint4* cwv, const uint8_t* cwt, const uint4* np1, const uint8_t* s0,
-                 uint32_t d, uint64_t total, PrefixTable* out, hipStream_t st) {
+int reuse_prefix(dcf_prg* p, const Cfg& c, Workspace* w, int party, const KeyBlock& kb, const uint8_t* s0, uint32_t d,
+                 uint64_t total, PrefixTable* out, hipStream_t st) {
+  const size_t n_bytes = kb.nlev / 8;
+  const uint8_t* cwb = kb.cws;  // the block's start: what the hints remember
+  const uint4 *cws = kb.s4(), *cwv = kb.v4();
+  const uint8_t* cwt = kb.cwt;
   Workspace::PrefixHints& h = w->ph;
   // dcf_prg_last_eval_blocks: at automatic depth the table is the library's own choice and part of
   // what the call encrypts, so the build / deepening that really ran is counted; a forced depth
@@ -810,7 +844,7 @@ int reuse_prefix(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, int par
     // that runs whatever the state said.
     check(1u);
     HIP_TRY(hipGetLastError());
-    if (int rc = try_prefix(p, c, w, n_bytes, party, cws, cwv, cwt, np1, s0, d, out, st, w->d_pst)) return rc;
+    if (int rc = try_prefix(p, c, w, party, kb, s0, d, out, st, w->d_pst)) return rc;
     if (!out->levels) return DCF_OK;  // (h.valid is false: build_prefix cleared it)
     launch_commit(w, st, 0u, out->levels, 0xFFFFFFFFu, counted * ((2ull << out->levels) - 2));
     HIP_TRY(hipGetLastError());
@@ -890,7 +924,7 @@ int reuse_prefix(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, int par
   // The key changed under the same pointers (state 0 after the check, or after a deepening that
   // found another depth than the host expected): rebuild at the first-call depth; else nothing runs.
   const Workspace::PrefixHints keep = h;  // (build_prefix clears the hints)
-  if (int rc = build_prefix(p, w, party, cws, cwv, cwt, np1, s0, keep.base, out, st, w->d_pst)) return rc;
+  if (int rc = build_prefix(p, w, party, kb, s0, keep.base, out, st, w->d_pst)) return rc;
   launch_commit(w, st, 0u, keep.base, 0xFFFFFFFFu, counted * ((2ull << keep.base) - 2));
   HIP_TRY(hipGetLastError());
   h = keep;
@@ -899,13 +933,27 @@ int reuse_prefix(dcf_prg* p, const Cfg& c, Workspace* w, size_t n_bytes, int par
   return DCF_OK;
 }
 
-// Tails over cnt points of cnt / ppk consecutive keys key, key + 1, ... (ppk points each, s0: their
-// s0s back to back; one key: ppk = cnt); grid rows = keys x ranges per key.
+// One tail pass, y[32, LAMBDA) from the head's t-vectors: cnt points of cnt / ppk consecutive keys key,
+// key + 1, ... of the block (ppk points each, s0: their s0s back to back; one key: ppk = cnt).
+struct WideTail {
+  KeyBlock kb;
+  uint64_t key;
+  const uint8_t* s0;
+  uint32_t* tvec;
+  uint64_t cnt, ppk;
+  uint8_t* ys;
+  int party;
+  hipStream_t st;
+  int cus;
+  Workspace* w;
+};
+
+// The 4-bit tail; grid rows = keys x ranges per key.
 template <int TW, int NCH = 0, bool ACC = false>
-int launch_tail(const uint8_t* cws, const uint8_t* cwv, const uint8_t* np1, const uint8_t* s0, uint32_t nlev,
-                uint32_t lam, uint64_t K, uint64_t key, const uint32_t* tvec, uint64_t cnt, uint8_t* ys,
-                hipStream_t st, uint64_t ppk, uint32_t c0 = 0, uint32_t ncp = 0) {
+int launch_tail(const WideTail& t, uint32_t c0 = 0, uint32_t ncp = 0) {
   static_assert(TW == 32 || TW == 64 || TW == 128 || TW == 256, "tile width");
+  const uint32_t nlev = t.kb.nlev, lam = t.kb.lam;
+  const uint64_t cnt = t.cnt, ppk = t.ppk;
   if (ncp == 0) ncp = (nlev + 1 + 3) / 4;
   const size_t lds = (size_t)ncp * 16 * TW;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eval_wide_tail<TW, NCH, ACC>),
@@ -916,8 +964,9 @@ int launch_tail(const uint8_t* cws, const uint8_t* cwv, const uint8_t* np1, cons
   const uint64_t tiles = (lam + TW - 1) / TW;
   const uint64_t rpk = (ppk + kTailPts - 1) / kTailPts;
   const dim3 grid((unsigned)tiles, (unsigned)((cnt / ppk) * rpk));
-  hipLaunchKernelGGL((k_eval_wide_tail<TW, NCH, ACC>), grid, dim3(kBlock), lds, st, cws, cwv, np1, s0, nlev, lam, K,
-                     key, tvec, cnt, kTailPts, ys, t_words(nlev), ppk, (uint32_t)rpk, c0, ncp);
+  hipLaunchKernelGGL((k_eval_wide_tail<TW, NCH, ACC>), grid, dim3(kBlock), lds, t.st, t.kb.cws, t.kb.cwv, t.kb.np1, t.s0,
+                     nlev, lam, t.kb.K, t.key, (const uint32_t*)t.tvec, cnt, kTailPts, t.ys, t_words(nlev), ppk,
+                     (uint32_t)rpk, c0, ncp);
   HIP_TRY(hipGetLastError());
   return DCF_OK;
 }
@@ -925,16 +974,11 @@ int launch_tail(const uint8_t* cws, const uint8_t* cwv, const uint8_t* np1, cons
 // More chunks than one 32-byte-tile table set holds (N >= 160): passes of kTailPassChunks chunks,
 // each after the first adding its rows' share to the y the previous pass wrote.
 constexpr uint32_t kTailPassChunks = 320;  // 320 x 16 entries x 32 B = 160 KiB
-int launch_tail_passes(const uint8_t* cws, const uint8_t* cwv, const uint8_t* np1, const uint8_t* s0, uint32_t nlev,
-                       uint32_t lam, uint64_t K, uint64_t key, const uint32_t* tvec, uint64_t cnt, uint8_t* ys,
-                       hipStream_t st, uint64_t ppk) {
-  const uint32_t nch = (nlev + 1 + 3) / 4;
+int launch_tail_passes(const WideTail& t) {
+  const uint32_t nch = (t.kb.nlev + 1 + 3) / 4;
   for (uint32_t c0 = 0; c0 < nch; c0 += kTailPassChunks) {
     const uint32_t ncp = std::min(kTailPassChunks, nch - c0);
-    const int rc = c0 == 0 ? launch_tail<32>(cws, cwv, np1, s0, nlev, lam, K, key, tvec, cnt, ys, st, ppk, 0, ncp)
-                           : launch_tail<32, 0, true>(cws, cwv, np1, s0, nlev, lam, K, key, tvec, cnt, ys, st, ppk,
-                                                      c0, ncp);
-    if (rc) return rc;
+    if (int rc = c0 == 0 ? launch_tail<32>(t, 0, ncp) : launch_tail<32, 0, true>(t, c0, ncp)) return rc;
   }
   return DCF_OK;
 }
@@ -944,13 +988,15 @@ int launch_tail_passes(const uint8_t* cws, const uint8_t* cwv, const uint8_t* np
 // global memory beside the LDS tables, read through the vector L1 / L2, measured 11-24 % slower on
 // C4: profiles/AB_LOG.md r04d.)
 template <int R6, int R5, int ROW0>
-int launch_tail2(const uint8_t* cws, const uint8_t* cwv, const uint8_t* np1, const uint8_t* s0, uint32_t nlev,
-                 uint32_t lam, uint64_t K, uint64_t key, uint32_t* tvec, uint64_t cnt, uint8_t* ys, hipStream_t st,
-                 int cus, uint64_t ppk, int party, Workspace* w) {
+int launch_tail2(const WideTail& t) {
   using L = Tail2Layout<R6, R5, ROW0>;
+  const uint32_t nlev = t.kb.nlev, lam = t.kb.lam;
+  const uint64_t cnt = t.cnt, ppk = t.ppk;
+  hipStream_t st = t.st;
+  Workspace* w = t.w;
   if (nlev + 1 > L::rows()) return fail(DCF_ERR_UNSUPPORTED, "tail2 layout too small");
   const uint64_t tiles = (lam + 127) / 128;
-  hipLaunchKernelGGL((k_tvec_chunks<R6, R5, ROW0>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, tvec, nlev,
+  hipLaunchKernelGGL((k_tvec_chunks<R6, R5, ROW0>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, t.tvec, nlev,
                      cnt);
   HIP_TRY(hipGetLastError());
   const size_t lds = L::lds_bytes();
@@ -966,7 +1012,7 @@ int launch_tail2(const uint8_t* cws, const uint8_t* cwv, const uint8_t* np1, con
   // 33.08-33.12 / 33.12-33.41 / 33.24-33.28 / 33.69-33.99 ms.
   // Several keys (ppk < cnt): each key's points are ranges of their own (its own tables).
   constexpr uint64_t kTail2Rounds = 8;
-  const uint64_t ranges = std::max<uint64_t>(1, (uint64_t)cus * kTail2Rounds / tiles);
+  const uint64_t ranges = std::max<uint64_t>(1, (uint64_t)t.cus * kTail2Rounds / tiles);
   const uint64_t per = std::max<uint64_t>(32768, (((cnt + ranges - 1) / ranges) + 255) & ~(uint64_t)255);
   const uint64_t rpk = (ppk + per - 1) / per;
   const dim3 grid((unsigned)tiles, (unsigned)((cnt / ppk) * rpk));
@@ -977,32 +1023,29 @@ int launch_tail2(const uint8_t* cws, const uint8_t* cwv, const uint8_t* np1, con
     w->d_tctr = reinterpret_cast<uint32_t*>(b);
     gctr = w->d_tctr;
   }
-  hipLaunchKernelGGL((k_eval_wide_tail2<R6, R5, ROW0>), grid, dim3(kBlock), lds, st, cws, cwv, np1, s0, nlev, lam, K,
-                     key, tvec, cnt, (uint32_t)per, ys, ppk, (uint32_t)rpk, (uint32_t)party, gctr);
+  hipLaunchKernelGGL((k_eval_wide_tail2<R6, R5, ROW0>), grid, dim3(kBlock), lds, st, t.kb.cws, t.kb.cwv, t.kb.np1, t.s0,
+                     nlev, lam, t.kb.K, t.key, t.tvec, cnt, (uint32_t)per, t.ys, ppk, (uint32_t)rpk, (uint32_t)t.party,
+                     gctr);
   HIP_TRY(hipGetLastError());
   return DCF_OK;
 }
 
 // The tail for n = nlev levels: the paired-slot tail when one of its instances covers the
 // n + 1 rows with fewer LDS reads than the 4-bit tail's ceil((n + 1) / 4), else the 4-bit one.
-// ppk: points per key (= cnt for one key).
-int run_tail(const uint8_t* cws, const uint8_t* cwv, const uint8_t* np1, const uint8_t* s0, uint32_t nlev,
-             uint32_t lam, uint64_t K, uint64_t key, uint32_t* tvec, uint64_t cnt, uint8_t* ys, hipStream_t st,
-             int cus, uint64_t ppk, int party, Workspace* w) {
-  const uint32_t nrows = nlev + 1, nch = (nrows + 3) / 4;
-  if (lam % 128 == 0) {
+int run_tail(const WideTail& t) {
+  const uint32_t nrows = t.kb.nlev + 1, nch = (nrows + 3) / 4;
+  if (t.kb.lam % 128 == 0) {
     // Paired-slot layouts with row 0 folded into the constant (t_0 = party): the first that covers
     // rows 1 .. n, in increasing reads per 16 bytes of y (2 (R6 + R5)), used when it beats the
     // 4-bit tail's ceil((n + 1) / 4).  (r04 layouts, row 0 in the tables: N = 16 took (5, 7), 24 reads.)
-#define DCF_T2(A, B)                                                                               \
-  if (nrows <= Tail2Layout<A, B, 1>::rows() && 2u * (A + B) < nch)                                 \
-    return launch_tail2<A, B, 1>(cws, cwv, np1, s0, nlev, lam, K, key, tvec, cnt, ys, st, cus, ppk, party, w);
+#define DCF_T2(A, B) \
+  if (nrows <= Tail2Layout<A, B, 1>::rows() && 2u * (A + B) < nch) return launch_tail2<A, B, 1>(t);
 #ifndef DCF_T2_ROW0
 #define DCF_T2_ROW0 1
 #endif
     if (!DCF_T2_ROW0) {  // A/B knob: the r04 layouts (row 0 in the tables)
       if (nrows <= Tail2Layout<5, 7>::rows() && nrows > Tail2Layout<3, 3>::rows() && 24u < nch)
-        return launch_tail2<5, 7, 0>(cws, cwv, np1, s0, nlev, lam, K, key, tvec, cnt, ys, st, cus, ppk, party, w);
+        return launch_tail2<5, 7, 0>(t);
     }
     DCF_T2(0, 1)   // N = 1: 8 rows, 2 reads (4-bit: 3)
     DCF_T2(2, 0)   // N = 2, 3: 16 / 24 rows, 4 reads (5 / 7)
@@ -1019,72 +1062,80 @@ int run_tail(const uint8_t* cws, const uint8_t* cwv, const uint8_t* np1, const u
 #undef DCF_T2
   }
   // 4-bit tail: the widest tile whose tables (nch x 16 entries x TW bytes) fit the LDS
-  if (nch == 33) return launch_tail<256, 33>(cws, cwv, np1, s0, nlev, lam, K, key, tvec, cnt, ys, st, ppk);
-  if (nch <= 40) return launch_tail<256>(cws, cwv, np1, s0, nlev, lam, K, key, tvec, cnt, ys, st, ppk);
-  if (nch <= 80) return launch_tail<128>(cws, cwv, np1, s0, nlev, lam, K, key, tvec, cnt, ys, st, ppk);
-  if (nch <= 160) return launch_tail<64>(cws, cwv, np1, s0, nlev, lam, K, key, tvec, cnt, ys, st, ppk);
-  if (nch <= kTailPassChunks) return launch_tail<32>(cws, cwv, np1, s0, nlev, lam, K, key, tvec, cnt, ys, st, ppk);
-  return launch_tail_passes(cws, cwv, np1, s0, nlev, lam, K, key, tvec, cnt, ys, st, ppk);
+  if (nch == 33) return launch_tail<256, 33>(t);
+  if (nch <= 40) return launch_tail<256>(t);
+  if (nch <= 80) return launch_tail<128>(t);
+  if (nch <= 160) return launch_tail<64>(t);
+  if (nch <= kTailPassChunks) return launch_tail<32>(t);
+  return launch_tail_passes(t);
 }
 
-// Dcf::eval at LAMBDA >= 32 for key `key` of a K-key CWB (see kernels_wide.h).
+// The CW digest of the wide stream head (bytes [0,32) of each level's cw_s / cw_v, then the cw_t bytes): 65 B
+// per level and key in w->d_dig.  dig_levels: the levels the buffer holds.
+constexpr size_t kDigLevelBytes = 65;
+int ensure_dig(Workspace* w, uint64_t levels, hipStream_t st) {
+  if (w->dig_levels >= levels) return DCF_OK;
+  size_t have = (size_t)w->dig_levels * kDigLevelBytes;
+  const int rc = grow(&w->d_dig, &have, (size_t)levels * kDigLevelBytes, st);
+  w->dig_levels = (uint32_t)(have / kDigLevelBytes);
+  return rc;
+}
+
+// The digest of keys [k0, k0 + nk) of the block, key-major, the cw_t bytes behind the nk keys' rows.
+int launch_digest(Workspace* w, const KeyBlock& kb, uint64_t k0, uint64_t nk, hipStream_t st) {
+  hipLaunchKernelGGL(k_cw_digest, dim3((unsigned)((4 * kb.nlev * nk + 255) / 256)), dim3(256), 0, st, kb.cws, kb.cwv,
+                     kb.cwt, kb.nlev, kb.lam, kb.K, k0, (uint32_t)nk, (uint4*)w->d_dig,
+                     w->d_dig + (size_t)nk * kb.nlev * 64);
+  HIP_TRY(hipGetLastError());
+  return DCF_OK;
+}
+
+// One head/tail pass over the points of `t` (xs: theirs), whose keys' digest is in w->d_dig: the pass's work
+// counter, the stream head (one point per lane, one 1024-thread workgroup per CU: the T-tables fill the LDS;
+// 2.5 AES blocks per level instead of 4), then the tail when LAMBDA > 32.  mk: a point's key is
+// t.key + point / t.ppk (the batched engine), else every point is key t.key's and may start below wpf.
+int wide_pass(dcf_prg* p, const WideTail& t, const uint8_t* xs, bool mk, const WidePrefix& wpf) {
+  Workspace* w = t.w;
+  const uint32_t nlev = t.kb.nlev, lam = t.kb.lam, n_bytes = nlev / 8;
+  HIP_TRY(hipMemsetAsync(w->d_ctr, 0, 8, t.st));  // (the block count beside it stays)
+  const uint64_t units = (t.cnt + kWideUnit - 1) / kWideUnit;
+  const uint64_t blocks = std::min<uint64_t>((units + 15) / 16, (uint64_t)p->cus);
+  const uint8_t* dig_t = w->d_dig + (size_t)(t.cnt / t.ppk) * nlev * 64;
+  const bool xreg = n_bytes % 4 == 0 && n_bytes <= 16;
+#define DCF_WH(MH, XR) \
+  { k_eval_wide_head_stream<1, MH, XR, false, kBlock>, k_eval_wide_head_stream<1, MH, XR, true, kBlock> }
+  static constexpr decltype(&k_eval_wide_head_stream<1, false, false, false, kBlock>) kHead[2][2][2] = {
+      {DCF_WH(false, false), DCF_WH(false, true)}, {DCF_WH(true, false), DCF_WH(true, true)}};  // [MASK_HEAD][XREG][MK]
+#undef DCF_WH
+  hipLaunchKernelGGL(kHead[lam == 32][xreg][mk], dim3((unsigned)blocks), dim3(kBlock), 0, t.st, p->d_tab, p->d_rk2,
+                     (const uint4*)w->d_dig, dig_t, t.kb.np1, t.s0, (uint32_t)t.party, xs, n_bytes, lam, t.kb.K, t.key,
+                     t.cnt, w->d_ctr, t.ys, t.tvec, wpf, t_words(nlev), (uint32_t)t.ppk);
+  HIP_TRY(hipGetLastError());
+  return lam > 32 ? run_tail(t) : DCF_OK;
+}
+
+// The t-vector scratch of a pass of `points` points; + 256 B: a multi-pass tail's t loads run up to 64 B past
+// the last row (never used).
+size_t wide_tvec_bytes(uint64_t points, uint32_t tw) { return align256(points * tw * 4) + 256; }
+
+// Dcf::eval at LAMBDA >= 32 for key `key` of the block (see kernels_wide.h): the key's digest and, at depth
+// d > 0 (the plan's wide_prefix_depth), its shared-prefix table once, then the m points in passes that share both.
 // The caller (eval_launch) has zeroed the workspace's block count once for the whole call.
-// d: the shared-prefix depth of the call's plan (wide_prefix_depth), 0 for none.
-int eval_wide(dcf_prg* p, uint32_t d, Workspace* w, size_t n_bytes, uint64_t K, uint64_t key, int party, const uint8_t* cwb,
-              const uint8_t* s0, const uint8_t* xs, uint64_t m, uint8_t* ys, hipStream_t st) {
-  const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * n_bytes);
-  const size_t n = 8 * n_bytes;
-  const uint8_t* cws = cwb;
-  const uint8_t* cwv = cwb + n * K * lam;
-  const uint8_t* cwt = cwb + 2 * n * K * lam;
-  const uint8_t* np1 = cwb + dcf_cwb_np1_offset(n_bytes, lam, K);
-  const uint32_t tw = t_words(nlev);  // t-vector words per point
+int eval_wide(dcf_prg* p, uint32_t d, Workspace* w, const KeyBlock& kb, uint64_t key, int party, const uint8_t* s0,
+              const uint8_t* xs, uint64_t m, uint8_t* ys, hipStream_t st) {
+  const uint32_t tw = t_words(kb.nlev);  // t-vector words per point
   const uint64_t chunk = std::min<uint64_t>(m, wide_chunk_points(tw));
-  // + 256 B: a multi-pass tail's t loads run up to 64 B past the last row (never used)
-  const size_t tvb = ((chunk * tw * 4 + 255) & ~(size_t)255) + 256;
-  int rc = ensure_ws(w, tvb, st);
-  if (rc) return rc;
-  uint32_t* tvec = reinterpret_cast<uint32_t*>(w->d_ws);
+  if (int rc = ensure_ws(w, wide_tvec_bytes(chunk, tw), st)) return rc;
+  if (int rc = ensure_dig(w, kb.nlev, st)) return rc;
+  if (int rc = launch_digest(w, kb, key, 1, st)) return rc;
   WidePrefix wpf{nullptr, 0u};
+  if (d)
+    if (int rc = build_wide_prefix(p, w, kb.nlev, party, s0, d, &wpf, st)) return rc;
+  w->last_prefix = d;
   for (uint64_t off = 0; off < m; off += chunk) {
-    const uint64_t cnt = (m - off < chunk) ? m - off : chunk;
-    {  // stream head: 2.5 AES blocks per level instead of 4
-      HIP_TRY(hipMemsetAsync(w->d_ctr, 0, 8, st));  // the pass's work counter (the block count stays)
-      if (off == 0) {  // CW digest of this key (bytes [0,32) of each level's cw_s / cw_v, and cw_t)
-        if (w->dig_levels < nlev) {
-          size_t have = (size_t)w->dig_levels * 65;
-          if (int rc2 = grow(&w->d_dig, &have, (size_t)nlev * 65, st)) return rc2;
-          w->dig_levels = nlev;
-        }
-        hipLaunchKernelGGL(k_cw_digest, dim3((4 * nlev + 255) / 256), dim3(256), 0, st, cws, cwv, cwt, nlev, lam, K,
-                           key, 1u, (uint4*)w->d_dig, w->d_dig + (size_t)nlev * 64);
-        HIP_TRY(hipGetLastError());
-        if (d) {
-          rc = build_wide_prefix(p, w, nlev, party, s0, d, &wpf, st);
-          if (rc) return rc;
-        }
-        w->last_prefix = d;
-      }
-      const uint64_t units = (cnt + kWideUnit - 1) / kWideUnit;
-      uint64_t blocks = (units + 15) / 16;
-      if (blocks > (uint64_t)p->cus) blocks = (uint64_t)p->cus;
-      // one point per lane, one 1024-thread workgroup per CU (the T-tables fill the LDS)
-#define DCF_WHS(MH, XR)                                                                                        \
-  hipLaunchKernelGGL((k_eval_wide_head_stream<1, MH, XR, false, kBlock>), dim3((unsigned)blocks), dim3(kBlock), 0, st, p->d_tab, \
-                     p->d_rk2, (const uint4*)w->d_dig, w->d_dig + (size_t)nlev * 64, np1, s0, (uint32_t)party, xs + off * n_bytes, (uint32_t)n_bytes,   \
-                     lam, K, key, cnt, w->d_ctr, ys + off * lam, tvec, wpf, tw, (uint32_t)cnt)
-      const bool xreg = n_bytes % 4 == 0 && n_bytes <= 16;
-      if (lam == 32 && xreg) DCF_WHS(true, true);
-      else if (lam == 32) DCF_WHS(true, false);
-      else if (xreg) DCF_WHS(false, true);
-      else DCF_WHS(false, false);
-#undef DCF_WHS
-    }
-    HIP_TRY(hipGetLastError());
-    if (lam > 32) {
-      rc = run_tail(cws, cwv, np1, s0, nlev, lam, K, key, tvec, cnt, ys + off * lam, st, p->cus, cnt, party, w);
-      if (rc) return rc;
-    }
+    const uint64_t cnt = std::min<uint64_t>(chunk, m - off);
+    const WideTail t{kb, key, s0, (uint32_t*)w->d_ws, cnt, cnt, ys + off * kb.lam, party, st, p->cus, w};
+    if (int rc = wide_pass(p, t, xs + off * (kb.nlev / 8), false, wpf)) return rc;
   }
   return DCF_OK;
 }
@@ -1094,55 +1145,21 @@ int eval_wide(dcf_prg* p, uint32_t d, Workspace* w, size_t n_bytes, uint64_t K, 
 // point / ppk) and one tail launch whose workgroups build the tables of their own key.  For the
 // shapes of wide_batched() (ppk <= kWideBatchPpk).  No shared prefix; the MMO PRG keeps the
 // per-key path.
-int eval_wide_batch(dcf_prg* p, Workspace* w, size_t n_bytes, uint64_t K, uint64_t ppk, int party,
-                    const uint8_t* cwb, const uint8_t* s0s, const uint8_t* xs, uint8_t* ys, hipStream_t st) {
-  const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * n_bytes);
-  const size_t n = 8 * n_bytes;
-  const uint8_t* cws = cwb;
-  const uint8_t* cwv = cwb + n * K * lam;
-  const uint8_t* cwt = cwb + 2 * n * K * lam;
-  const uint8_t* np1 = cwb + dcf_cwb_np1_offset(n_bytes, lam, K);
-  const uint32_t tw = t_words(nlev);
+int eval_wide_batch(dcf_prg* p, Workspace* w, const KeyBlock& kb, uint64_t ppk, int party, const uint8_t* s0s,
+                    const uint8_t* xs, uint8_t* ys, hipStream_t st) {
+  const uint32_t nlev = kb.nlev, lam = kb.lam, tw = t_words(nlev);
   // keys per pass; the digest's uint4 index 4 * (key * nlev + level) and dig_levels are 32-bit
   const uint64_t kdig = std::max<uint64_t>(1, (0xFFFFFFFFull / 4u) / nlev);
   const uint64_t kp =
-      std::max<uint64_t>(1, std::min<uint64_t>({K, wide_chunk_points(tw) / ppk, kWideBatchKeys, kdig}));
-  const size_t tvb = ((kp * ppk * tw * 4 + 255) & ~(size_t)255) + 256;
-  if (int rc = ensure_ws(w, tvb, st)) return rc;
-  if (w->dig_levels < kp * nlev) {
-    size_t have = (size_t)w->dig_levels * 65;
-    if (int rc = grow(&w->d_dig, &have, (size_t)kp * nlev * 65, st)) return rc;
-    w->dig_levels = (uint32_t)(kp * nlev);
-  }
-  uint32_t* tvec = reinterpret_cast<uint32_t*>(w->d_ws);
+      std::max<uint64_t>(1, std::min<uint64_t>({kb.K, wide_chunk_points(tw) / ppk, kWideBatchKeys, kdig}));
+  if (int rc = ensure_ws(w, wide_tvec_bytes(kp * ppk, tw), st)) return rc;
+  if (int rc = ensure_dig(w, kp * nlev, st)) return rc;
   const WidePrefix none{nullptr, 0u};
-  const bool xreg = n_bytes % 4 == 0 && n_bytes <= 16;
-  for (uint64_t k0 = 0; k0 < K; k0 += kp) {
-    const uint64_t nk = std::min<uint64_t>(kp, K - k0), cnt = nk * ppk;
-    HIP_TRY(hipMemsetAsync(w->d_ctr, 0, 8, st));  // the pass's work counter (the block count stays)
-    uint4* dig = (uint4*)w->d_dig;
-    uint8_t* dig_t = w->d_dig + (size_t)nk * nlev * 64;
-    hipLaunchKernelGGL(k_cw_digest, dim3((unsigned)((4 * nlev * nk + 255) / 256)), dim3(256), 0, st, cws, cwv, cwt, nlev,
-                       lam, K, k0, (uint32_t)nk, dig, dig_t);
-    HIP_TRY(hipGetLastError());
-    const uint64_t units = (cnt + kWideUnit - 1) / kWideUnit;
-    const uint64_t blocks = std::min<uint64_t>((units + 15) / 16, (uint64_t)p->cus);
-    const uint8_t* s0p = s0s + k0 * lam;
-    const uint8_t* xp = xs + k0 * ppk * n_bytes;
-    uint8_t* yp = ys + k0 * ppk * lam;
-#define DCF_WHB(MH, XR)                                                                                           \
-  hipLaunchKernelGGL((k_eval_wide_head_stream<1, MH, XR, true, kBlock>), dim3((unsigned)blocks), dim3(kBlock), 0, st, \
-                     p->d_tab, p->d_rk2, (const uint4*)dig, dig_t, np1, s0p, (uint32_t)party, xp, (uint32_t)n_bytes,  \
-                     lam, K, k0, cnt, w->d_ctr, yp, tvec, none, tw, (uint32_t)ppk)
-    if (lam == 32 && xreg) DCF_WHB(true, true);
-    else if (lam == 32) DCF_WHB(true, false);
-    else if (xreg) DCF_WHB(false, true);
-    else DCF_WHB(false, false);
-#undef DCF_WHB
-    HIP_TRY(hipGetLastError());
-    if (lam > 32) {
-      if (int rc = run_tail(cws, cwv, np1, s0p, nlev, lam, K, k0, tvec, cnt, yp, st, p->cus, ppk, party, w)) return rc;
-    }
+  for (uint64_t k0 = 0; k0 < kb.K; k0 += kp) {
+    const uint64_t nk = std::min<uint64_t>(kp, kb.K - k0);
+    if (int rc = launch_digest(w, kb, k0, nk, st)) return rc;
+    const WideTail t{kb, k0, s0s + k0 * lam, (uint32_t*)w->d_ws, nk * ppk, ppk, ys + k0 * ppk * lam, party, st, p->cus, w};
+    if (int rc = wide_pass(p, t, xs + k0 * ppk * (nlev / 8), true, none)) return rc;
   }
   return DCF_OK;
 }
@@ -1150,15 +1167,10 @@ int eval_wide_batch(dcf_prg* p, Workspace* w, size_t n_bytes, uint64_t K, uint64
 // Dcf::eval with the MMO PRG at LAMBDA >= 32 for key `key` (kernels_mmo_wide.h): per pass
 // of up to kWideChunk points, the head walks block 0 (y[0:16), t-vector), then the tail
 // walks blocks 1..nb-1 given the t-vectors.
-int eval_mmo_wide(dcf_prg* p, Workspace* w, size_t n_bytes, uint64_t K, uint64_t key, int party, const uint8_t* cwb,
-                  const uint8_t* s0, const uint8_t* xs, uint64_t m, uint8_t* ys, hipStream_t st) {
-  const uint32_t lam = (uint32_t)p->lambda, nb = lam / 16u;
-  const size_t n = 8 * n_bytes;
-  const uint8_t* cws = cwb;
-  const uint8_t* cwv = cwb + n * K * lam;
-  const uint8_t* cwt = cwb + 2 * n * K * lam;
-  const uint8_t* np1 = cwb + dcf_cwb_np1_offset(n_bytes, lam, K);
-  const uint32_t tw = mmo_t_words((uint32_t)n);
+int eval_mmo_wide(dcf_prg* p, Workspace* w, const KeyBlock& kb, uint64_t key, int party, const uint8_t* s0,
+                  const uint8_t* xs, uint64_t m, uint8_t* ys, hipStream_t st) {
+  const uint32_t lam = kb.lam, nb = lam / 16u, n_bytes = kb.nlev / 8;
+  const uint32_t tw = mmo_t_words(kb.nlev);
   const uint64_t chunk = std::min<uint64_t>(m, wide_chunk_points(2 * tw));
   if (int rc = ensure_ws(w, chunk * tw * 4, st)) return rc;
   uint32_t* tvec = reinterpret_cast<uint32_t*>(w->d_ws);
@@ -1166,14 +1178,15 @@ int eval_mmo_wide(dcf_prg* p, Workspace* w, size_t n_bytes, uint64_t K, uint64_t
     const uint64_t cnt = std::min<uint64_t>(chunk, m - off);
     const uint64_t groups = (cnt + 63) / 64;
     const dim3 gh((unsigned)std::min<uint64_t>((groups + 15) / 16, (uint64_t)p->cus));
-    hipLaunchKernelGGL(k_mmo_wide_eval<true>, gh, dim3(kBlock), 0, st, p->d_tab, p->d_rk128, cws, cwv, cwt, np1, s0,
-                       (uint32_t)party, xs + off * n_bytes, (uint32_t)n_bytes, lam, K, key, cnt, tvec, ys + off * lam);
+    hipLaunchKernelGGL(k_mmo_wide_eval<true>, gh, dim3(kBlock), 0, st, p->d_tab, p->d_rk128, kb.cws, kb.cwv, kb.cwt,
+                       kb.np1, s0, (uint32_t)party, xs + off * n_bytes, n_bytes, lam, kb.K, key, cnt, tvec,
+                       ys + off * lam);
     HIP_TRY(hipGetLastError());
     if (nb > 1) {
       const uint64_t items = groups * (nb - 1);
       const dim3 gt((unsigned)std::min<uint64_t>((items + 15) / 16, 4 * (uint64_t)p->cus));
-      hipLaunchKernelGGL(k_mmo_wide_eval<false>, gt, dim3(kBlock), 0, st, p->d_tab, p->d_rk128, cws, cwv, cwt, np1,
-                         s0, (uint32_t)party, xs + off * n_bytes, (uint32_t)n_bytes, lam, K, key, cnt, tvec,
+      hipLaunchKernelGGL(k_mmo_wide_eval<false>, gt, dim3(kBlock), 0, st, p->d_tab, p->d_rk128, kb.cws, kb.cwv, kb.cwt,
+                         kb.np1, s0, (uint32_t)party, xs + off * n_bytes, n_bytes, lam, kb.K, key, cnt, tvec,
                          ys + off * lam);
       HIP_TRY(hipGetLastError());
     }
@@ -1183,10 +1196,11 @@ int eval_mmo_wide(dcf_prg* p, Workspace* w, size_t n_bytes, uint64_t K, uint64_t
 
 // Batched Dcf::gen with the MMO PRG at LAMBDA >= 32 (kernels_mmo_wide.h): per pass of keys,
 // the head over block 0 of both parties (t-CWs, per-level t bits), then the tail.
-int gen_mmo_wide(dcf_prg* p, Workspace* w, size_t n_bytes, uint64_t K, const uint8_t* alpha, const uint8_t* beta,
-                 const uint8_t* s0_0, const uint8_t* s0_1, int bound, uint8_t* cws, uint8_t* cwv, uint8_t* cwt,
-                 uint8_t* np1, hipStream_t st) {
-  const uint32_t lam = (uint32_t)p->lambda, nb = lam / 16u, nlev = (uint32_t)(8 * n_bytes);
+int gen_mmo_wide(dcf_prg* p, Workspace* w, const KeyBlockOut& kb, const uint8_t* alpha, const uint8_t* beta,
+                 const uint8_t* s0_0, const uint8_t* s0_1, int bound, hipStream_t st) {
+  const uint32_t lam = kb.lam, nb = lam / 16u, nlev = kb.nlev, n_bytes = nlev / 8;
+  const uint64_t K = kb.K;
+  uint8_t *cws = kb.cws, *cwv = kb.cwv, *cwt = kb.cwt, *np1 = kb.np1;
   if (int rc = ensure_ws(w, (size_t)K * nlev * 4, st)) return rc;
   uint32_t* tinfo = reinterpret_cast<uint32_t*>(w->d_ws);
   const uint64_t groups = (K + 63) / 64;
@@ -1411,7 +1425,7 @@ size_t dcf_prg_device_bytes(const dcf_prg* p) {
   for (const Workspace* w : p->all_ws) {
     if (w->d_ctr) b += kCtrBytes;
     if (w->d_pst) b += kPfxStateBytes;
-    b += (size_t)w->dig_levels * 65 + w->kdig_bytes + w->ws_bytes + w->pfx_bytes +
+    b += (size_t)w->dig_levels * kDigLevelBytes + w->kdig_bytes + w->ws_bytes + w->pfx_bytes +
          w->d_stage_bytes + w->mkey_bytes + w->tctr_bytes + w->fold_bytes;
   }
   return b;
@@ -1532,13 +1546,10 @@ static int gen_launch(dcf_prg* p, Lease& L, size_t n_bytes, size_t num_keys, con
                       const uint8_t* beta, const uint8_t* s0_0, const uint8_t* s0_1, int bound, uint8_t* cwb_out) {
   Workspace* w = L.w;
   hipStream_t st = L.st;
-  const size_t n = 8 * n_bytes, lam = p->lambda;
-  uint8_t* cws = cwb_out;
-  uint8_t* cwv = cwb_out + n * num_keys * lam;
-  uint8_t* cwt = cwb_out + 2 * n * num_keys * lam;
-  uint8_t* np1 = cwb_out + dcf_cwb_np1_offset(n_bytes, lam, num_keys);
-  if (p->kind == 1 && lam > 16) return gen_mmo_wide(p, w, n_bytes, num_keys, alpha, beta, s0_0, s0_1, bound, cws, cwv,
-                                                    cwt, np1, st);
+  const size_t lam = p->lambda;
+  const KeyBlockOut kb(cwb_out, n_bytes, lam, num_keys);
+  uint8_t *cws = kb.cws, *cwv = kb.cwv, *cwt = kb.cwt, *np1 = kb.np1;
+  if (p->kind == 1 && lam > 16) return gen_mmo_wide(p, w, kb, alpha, beta, s0_0, s0_1, bound, st);
   if (p->kind == 1) {  // Aes128MatyasMeyerOseasPrg (LAMBDA = 16)
     hipLaunchKernelGGL(k_gen16_mmo, dim3((unsigned)grid_for(num_keys, p->cus)), dim3(kBlock), 0, st, p->d_tab,
                        p->d_rk128, alpha, (const uint4*)beta, (const uint4*)s0_0, (const uint4*)s0_1, (uint32_t)bound,
@@ -1666,22 +1677,20 @@ struct EvalArgs {
   int party;
   const uint8_t *cwb, *s0s, *xs;
   uint8_t* ys;
-  const uint4 *cws, *cwv, *np1;
-  const uint8_t* cwt;
+  KeyBlock kb;
 };
 
 // LAMBDA >= 32, head/tail pipeline: keys with few points batched, else per key.
 static int eval_wide_engine(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs& a) {
   const size_t lam = p->lambda;
   phase_mark(p, L, 1);
-  if (plan.engine == Engine::WideBatch)
-    return eval_wide_batch(p, L.w, a.n_bytes, a.num_keys, a.ppk, a.party, a.cwb, a.s0s, a.xs, a.ys, L.st);
+  if (plan.engine == Engine::WideBatch) return eval_wide_batch(p, L.w, a.kb, a.ppk, a.party, a.s0s, a.xs, a.ys, L.st);
   for (uint64_t k = 0; k < a.num_keys; ++k) {
-    int rc = p->kind == 1 ? eval_mmo_wide(p, L.w, a.n_bytes, a.num_keys, k, a.party, a.cwb, a.s0s + k * lam,
-                                          a.xs + k * a.ppk * a.n_bytes, a.ppk, a.ys + k * a.ppk * lam, L.st)
-                          : eval_wide(p, plan.depth, L.w, a.n_bytes, a.num_keys, k, a.party, a.cwb, a.s0s + k * lam,
-                                      a.xs + k * a.ppk * a.n_bytes, a.ppk, a.ys + k * a.ppk * lam, L.st);
-    if (rc) return rc;
+    const uint8_t *s0 = a.s0s + k * lam, *xs = a.xs + k * a.ppk * a.n_bytes;
+    uint8_t* ys = a.ys + k * a.ppk * lam;
+    if (int rc = p->kind == 1 ? eval_mmo_wide(p, L.w, a.kb, k, a.party, s0, xs, a.ppk, ys, L.st)
+                              : eval_wide(p, plan.depth, L.w, a.kb, k, a.party, s0, xs, a.ppk, ys, L.st))
+      return rc;
   }
   return DCF_OK;
 }
@@ -1690,11 +1699,11 @@ static int eval_wide_engine(dcf_prg* p, Lease& L, const EvalPlan& plan, const Ev
 static int eval_mmo16(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs& a) {
   static constexpr decltype(&k_eval16_mmo<0>) kKernel[3] = {k_eval16_mmo<0>, k_eval16_mmo<1>, k_eval16_mmo<2>};
   PrefixTable pf{nullptr, 0u};
-  if (int rc = try_prefix(p, L.c, L.w, a.n_bytes, a.party, a.cws, a.cwv, a.cwt, a.np1, a.s0s, plan.depth, &pf, L.st))
+  if (int rc = try_prefix(p, L.c, L.w, a.party, a.kb, a.s0s, plan.depth, &pf, L.st))
     return rc;
   phase_mark(p, L, 1);
   hipLaunchKernelGGL(kKernel[plan.key_mode], dim3((unsigned)grid_for(a.total, p->cus)), dim3(kBlock), 0, L.st,
-                     p->d_tab, p->d_rk128, a.cws, a.cwv, a.cwt, a.np1, (const uint4*)a.s0s, (uint32_t)a.party, a.xs,
+                     p->d_tab, p->d_rk128, a.kb.s4(), a.kb.v4(), a.kb.cwt, a.kb.np14(), (const uint4*)a.s0s, (uint32_t)a.party, a.xs,
                      (uint32_t)a.n_bytes, (uint64_t)a.num_keys, (uint64_t)a.ppk, (uint4*)a.ys, pf);
   HIP_TRY(hipGetLastError());
   return DCF_OK;
@@ -1722,7 +1731,7 @@ static int eval_pair(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs&
   static constexpr decltype(&k_eval16_pair<0>) kKernel[3] = {k_eval16_pair<0>, k_eval16_pair<1>, k_eval16_pair<2>};
   const uint64_t total = a.total;
   PrefixTable spf{nullptr, 0u};
-  if (int rc = try_prefix(p, L.c, L.w, a.n_bytes, a.party, a.cws, a.cwv, a.cwt, a.np1, a.s0s, plan.depth, &spf, L.st))
+  if (int rc = try_prefix(p, L.c, L.w, a.party, a.kb, a.s0s, plan.depth, &spf, L.st))
     return rc;
   phase_mark(p, L, 1);
   // Whole waves per workgroup.  r06c (C1, same box, 4 alternating runs): rounding the lanes to a
@@ -1733,7 +1742,7 @@ static int eval_pair(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs&
   const dim3 g2((unsigned)((total * 2 + threads - 1) / threads)), b2((unsigned)threads);
   // (r06i: a per-lane block schedule for one key, k_eval16_pair2 — ~100 instead of 128 AES passes
   // per wave by simulation — ran 31 % slower on C1 and was removed; AB_LOG round 6)  Table: mode 0 only.
-  hipLaunchKernelGGL(kKernel[plan.key_mode], g2, b2, 0, L.st, p->d_tab, p->rk[0], a.cws, a.cwv, a.cwt, a.np1,
+  hipLaunchKernelGGL(kKernel[plan.key_mode], g2, b2, 0, L.st, p->d_tab, p->rk[0], a.kb.s4(), a.kb.v4(), a.kb.cwt, a.kb.np14(),
                      (const uint4*)a.s0s, (uint32_t)a.party, a.xs, (uint32_t)a.n_bytes, (uint64_t)a.num_keys,
                      (uint64_t)a.ppk, (uint4*)a.ys, p->d_rk0, plan.key_mode == 0 ? spf : PrefixTable{nullptr, 0u});
   HIP_TRY(hipGetLastError());
@@ -1787,12 +1796,12 @@ static int stream_multikey_prep(dcf_prg* p, Lease& L, const EvalArgs& a, PrefixT
     HIP_TRY(hipStreamWaitEvent(w->aux, w->aux_ev[0], 0));
     join.armed = true;
     hipLaunchKernelGGL(k_mk_prefix16<true>, dim3((unsigned)(((num_keys << kMkPfxRoot) + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, w->aux, p->d_tab, p->rk[0], a.cws, a.cwv, a.cwt, (const uint4*)a.s0s,
+                       dim3(kBlock), 0, w->aux, p->d_tab, p->rk[0], a.kb.s4(), a.kb.v4(), a.kb.cwt, (const uint4*)a.s0s,
                        (uint32_t)a.party, (uint64_t)num_keys, (uint4*)w->d_pfx, p->d_rk0, w->d_ctr);
     HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(k_cw_keymajor, dim3((unsigned)((num_keys + kKmKeys - 1) / kKmKeys), (unsigned)((n + kKmLevs - 1) / kKmLevs)),
-                     dim3(kKmThreads), 0, st, a.cws, a.cwv, a.cwt, (uint32_t)n, (uint64_t)num_keys, (uint4*)w->d_kdig,
+                     dim3(kKmThreads), 0, st, a.kb.s4(), a.kb.v4(), a.kb.cwt, (uint32_t)n, (uint64_t)num_keys, (uint4*)w->d_kdig,
                      w->d_kdig + (size_t)num_keys * n * 32);
   HIP_TRY(hipGetLastError());
   return DCF_OK;  // (the join runs here, as `join` leaves scope: the walk waits for the top trees)
@@ -1803,10 +1812,8 @@ static int stream_multikey_prep(dcf_prg* p, Lease& L, const EvalArgs& a, PrefixT
 // run a single-key table-start instance.
 static int stream_table(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArgs& a, PrefixTable* pf) {
   if (!(plan.depth && L.reuse && kSkPfx && (a.n_bytes == 16 || a.n_bytes == 4) && a.total < (1ull << 31)))
-    return try_prefix(p, L.c, L.w, a.n_bytes, a.party, a.cws, a.cwv, a.cwt, a.np1, a.s0s, plan.depth, pf, L.st);
-  if (int rc = reuse_prefix(p, L.c, L.w, a.n_bytes, a.party, a.cwb, a.cws, a.cwv, a.cwt, a.np1, a.s0s, plan.depth,
-                            a.total, pf, L.st))
-    return rc;
+    return try_prefix(p, L.c, L.w, a.party, a.kb, a.s0s, plan.depth, pf, L.st);
+  if (int rc = reuse_prefix(p, L.c, L.w, a.party, a.kb, a.s0s, plan.depth, a.total, pf, L.st)) return rc;
   L.w->last_prefix = pf->levels;
   L.w->last_prefix_dev = pf->levels != 0;
   return DCF_OK;
@@ -1827,8 +1834,8 @@ static int eval_stream(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArg
   const uint32_t* pst = w->last_prefix_dev ? w->d_pst : nullptr;  // cross-call table: its depth
   const bool xreg = n_bytes % 4 == 0 && n_bytes <= 16, multi = a.num_keys > 1;
   // several keys: the key-major digest of stream_multikey_prep
-  const uint4* scs = multi ? (const uint4*)w->d_kdig : a.cws;
-  const uint8_t* sct = multi ? w->d_kdig + (size_t)a.num_keys * n * 32 : a.cwt;
+  const uint4* scs = multi ? (const uint4*)w->d_kdig : a.kb.s4();
+  const uint8_t* sct = multi ? w->d_kdig + (size_t)a.num_keys * n * 32 : a.kb.cwt;
   const uint64_t kpl = multi ? mk_keys_per_launch(n_bytes, ppk) : 1;
   const uint64_t ppl = multi ? kpl * ppk : (1ull << 31);  // points per launch
   for (uint64_t c0 = 0; c0 < total; c0 += ppl) {
@@ -1841,14 +1848,14 @@ static int eval_stream(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArg
     const uint64_t blocks = std::min<uint64_t>((units + 15) / 16, (uint64_t)p->cus);
     const uint4* lcs = multi ? scs + k0 * 2 * n : scs;
     const uint8_t* lct = multi ? sct + k0 * n : sct;
-    const uint4* lnp1 = a.np1 + k0;
+    const uint4* lnp1 = a.kb.np14() + k0;
     const uint8_t* lxs = a.xs + c0 * n_bytes;
     uint8_t* lys = a.ys + c0 * 16;
     const uint8_t* ls0 = a.s0s + k0 * 16;
     const PrefixTable lpf = (multi && pf.levels) ? PrefixTable{pf.sv + 2 * (k0 << pf.levels), pf.levels} : pf;
 #define DCF_STREAM(XR, MK, PF, NBC, PK2, STG)                                                                        \
   hipLaunchKernelGGL((k_eval16_stream<NS, XR, MK, PF, NBC, PK2, STG>), dim3((unsigned)blocks), dim3(kBlock), 0, st,   \
-                     p->d_tab, p->rk[0], lcs, a.cwv, lct, lnp1, (const uint4*)ls0, (uint32_t)a.party, lxs,          \
+                     p->d_tab, p->rk[0], lcs, a.kb.v4(), lct, lnp1, (const uint4*)ls0, (uint32_t)a.party, lxs,          \
                      (uint32_t)n_bytes, (uint64_t)kc, (uint64_t)ppk, (uint64_t)cnt, w->d_ctr, (uint4*)lys, lpf,       \
                      p->d_rk0, pst)
     // multi-key: an instance for "per-key top trees present" (no root-seed start path: 48 -> 33
@@ -1891,7 +1898,7 @@ static int eval_ttable(dcf_prg* p, Lease& L, const EvalPlan& plan, const EvalArg
   static constexpr decltype(&k_eval16<0>) kKernel[3] = {k_eval16<0>, k_eval16<1>, k_eval16<2>};
   phase_mark(p, L, 1);
   hipLaunchKernelGGL(kKernel[plan.key_mode], dim3((unsigned)grid_for(a.total, p->cus)), dim3(kBlock), 0, L.st,
-                     p->d_tab, p->rk[0], a.cws, a.cwv, a.cwt, a.np1, (const uint4*)a.s0s, (uint32_t)a.party, a.xs,
+                     p->d_tab, p->rk[0], a.kb.s4(), a.kb.v4(), a.kb.cwt, a.kb.np14(), (const uint4*)a.s0s, (uint32_t)a.party, a.xs,
                      (uint32_t)a.n_bytes, (uint64_t)a.num_keys, (uint64_t)a.ppk, (uint4*)a.ys, L.w->d_ctr);
   HIP_TRY(hipGetLastError());
   return DCF_OK;
@@ -1924,10 +1931,8 @@ static int eval_launch(dcf_prg* p, Lease& L, size_t n_bytes, size_t num_keys, si
   L.w->last_prefix = 0;
   L.w->last_prefix_dev = false;
   phase_mark(p, L, 0);
-  const size_t n = 8 * n_bytes, lam = p->lambda;
-  const EvalArgs a{n_bytes, num_keys, ppk, (uint64_t)num_keys * ppk, party, cwb, s0s, xs, ys, (const uint4*)cwb,
-                   (const uint4*)(cwb + n * num_keys * lam),
-                   (const uint4*)(cwb + dcf_cwb_np1_offset(n_bytes, lam, num_keys)), cwb + 2 * n * num_keys * lam};
+  const EvalArgs a{n_bytes, num_keys, ppk, (uint64_t)num_keys * ppk, party, cwb, s0s, xs, ys,
+                   KeyBlock(cwb, n_bytes, p->lambda, num_keys)};
   const int rc = eval_body(p, L, plan, a);
   phase_mark(p, L, 2);
   p->last_ws.store(L.w);
@@ -2059,6 +2064,28 @@ static int host_lease(Lease& L) {
   return L.order(L.w->hs[1]);
 }
 
+// A host entry point's frame: the prg's device, a host lease, body(L), host_finish.
+extern "C++" template <class Body>
+static int host_call(dcf_prg* p, Body body) {
+  DeviceGuard dg(p->device);
+  if (!dg.ok) return fail(DCF_ERR_HIP, "hipSetDevice failed");
+  Lease L(p);
+  int rc = host_lease(L);
+  if (rc == DCF_OK) rc = body(L);
+  return host_finish(L, rc);
+}
+
+// The checks the host evals share ahead of their points (as check_eval_args for the device ones): `null_arg`
+// (the entry's own pointers), N, party, and the size of the one key against the prg's LAMBDA.
+static int check_host_key(bool null_arg, size_t n_bytes, int party, const dcf_prg* p, size_t cwb_len) {
+  if (null_arg) return fail(DCF_ERR_ARG, "null argument");
+  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
+  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
+  if (cwb_len != dcf_cwb_bytes(n_bytes, p->lambda, 1))
+    return fail(DCF_ERR_KEY, "key size does not match 8*N levels (lib.rs:165)");
+  return DCF_OK;
+}
+
 // Dcf::eval over host buffers (caller: DeviceGuard held, arguments checked, m > 0).
 // Tiny batches: one launch of a latency kernel (k_eval16_row / k_eval16_oct) that reads the key and points from, and writes
 // the outputs to, the workspace's mapped pinned buffer.  Otherwise chunks of `chunk` points
@@ -2184,8 +2211,10 @@ static int host_gen(dcf_prg* p, Lease& L, size_t nb, const uint8_t* alpha, const
   if (!tiny) HIP_TRY(hipMemcpyAsync(h + ok, d + ok, cwb_len, hipMemcpyDeviceToHost, sc));
   HIP_TRY(hipStreamSynchronize(sc));
   memcpy(cwb_out, h + ok, cwb_len);
-  if (tiny)  // the CWB's padding bytes (between cw_t and cw_np1) read 0, as on the staged path
-    memset(cwb_out + 2 * 8 * nb * lam + 8 * nb, 0, dcf_cwb_np1_offset(nb, lam, 1) - (2 * 8 * nb * lam + 8 * nb));
+  if (tiny) {  // the CWB's padding bytes (between cw_t and cw_np1) read 0, as on the staged path
+    const KeyBlockOut kb(cwb_out, nb, lam, 1);
+    memset(kb.cwt + kb.nlev, 0, kb.np1 - (kb.cwt + kb.nlev));
+  }
   return DCF_OK;
 }
 
@@ -2460,18 +2489,17 @@ static int range_end(dcf_prg* p, Lease& L) {
 // OUT: the tail's output policy; under RangeFold (h > 0 only) ys is row key0 of the call's `out`,
 // 16 bytes per key, zeroed by the caller, and op holds the group's rows of the table.
 extern "C++" template <class PRG, class KP, class OUT>
-static int range_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb, const uint8_t* s0s,
-                       uint64_t key0, uint64_t keys, const RangeX xa, uint64_t n, uint32_t h, size_t buf_bytes,
-                       uint8_t* ys, const OUT op) {
+static int range_group(dcf_prg* p, Lease& L, const KeyBlock& kb, int party, const uint8_t* s0s, uint64_t key0,
+                       uint64_t keys, const RangeX xa, uint64_t n, uint32_t h, size_t buf_bytes, uint8_t* ys,
+                       const OUT op) {
   using Idx = typename KP::Idx;
   hipStream_t st = L.st;
   Workspace* w = L.w;
-  const size_t lam = 16;
-  const uint32_t nlev = (uint32_t)(8 * nb);
-  const uint4* cws = (const uint4*)cwb + key0;
-  const uint4* cwv = (const uint4*)(cwb + (size_t)nlev * K * lam) + key0;
-  const uint8_t* cwt = cwb + 2 * (size_t)nlev * K * lam + key0;
-  const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(nb, lam, K)) + key0;
+  const uint32_t nlev = kb.nlev;
+  const size_t K = kb.K;
+  const KeyBlock g0 = kb.from(key0);  // the group's first key
+  const uint4 *cws = g0.s4(), *cwv = g0.v4(), *np1 = g0.np14();
+  const uint8_t* cwt = g0.cwt;
   const uint4* s0 = (const uint4*)s0s + key0;
   unsigned long long* blocks = reinterpret_cast<unsigned long long*>(w->d_ctr) + 1;
   const typename PRG::Arg rk = PRG::arg(p);
@@ -2522,15 +2550,12 @@ static int range_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, con
 // the workspace (RangePlan::wide_ws), built the CW digest of the group's keys (dig_t behind its
 // keys * 8N * 64 bytes) and zeroed the block count.
 extern "C++" template <bool MASK, class KP>
-static int range_wide_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party, const uint8_t* cwb,
-                            const uint8_t* s0s, uint64_t key0, uint64_t keys, const RangeX xa, uint64_t n, uint32_t h,
-                            const RangeWideWs& ws, uint8_t* ys) {
+static int range_wide_group(dcf_prg* p, Lease& L, const KeyBlock& kb, int party, const uint8_t* s0s, uint64_t key0,
+                            uint64_t keys, const RangeX xa, uint64_t n, uint32_t h, const RangeWideWs& ws, uint8_t* ys) {
   hipStream_t st = L.st;
   Workspace* w = L.w;
-  const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * nb);
-  const uint8_t* cwv = cwb + (size_t)nlev * K * lam;
-  const uint8_t* np1 = cwb + dcf_cwb_np1_offset(nb, lam, K);
-  const uint4* np1k = (const uint4*)(np1 + key0 * lam);  // the group's first key
+  const uint32_t lam = kb.lam, nlev = kb.nlev;
+  const uint4* np1k = kb.from(key0).np14();  // the group's first key
   const uint8_t* s0 = s0s + key0 * lam;
   const uint4* dig = (const uint4*)w->d_dig;
   const uint8_t* dig_t = w->d_dig + (size_t)keys * nlev * 64;
@@ -2574,7 +2599,7 @@ static int range_wide_group(dcf_prg* p, Lease& L, size_t nb, size_t K, int party
     HIP_TRY(hipGetLastError());
   }
   if (!MASK)  // y[32, lambda) from the t-vectors (the existing tail kernels)
-    return run_tail(cwb, cwv, np1, s0, nlev, lam, K, key0, tvec, keys * n, ys, st, p->cus, n, party, w);
+    return run_tail(WideTail{kb, key0, s0, tvec, keys * n, n, ys, party, st, p->cus, w});
   return DCF_OK;
 }
 
@@ -2598,11 +2623,12 @@ static int range_tree(dcf_prg* p, Lease& L, const RangePlan& pl, size_t nb, size
       pl.per_lane ? (mmo ? range_group<RangeMmo, RangeKeys, OUT> : range_group<RangeHirose, RangeKeys, OUT>)
                   : (mmo ? range_group<RangeMmo, RangeOneKey, OUT> : range_group<RangeHirose, RangeOneKey, OUT>);
   const uint64_t row = OUT::kFold ? 1 : cnt;  // rows of ys per key
+  const KeyBlock kb(cwb, nb, p->lambda, K);
   for (uint64_t k0 = key0; k0 < key0 + nkeys; k0 += pl.gkeys) {
     const uint64_t nk = std::min<uint64_t>(pl.gkeys, key0 + nkeys - k0);
     for (uint64_t o = 0; o < cnt; o += pl.per) {  // several keys to a group, or h = 0: cnt <= per, one pass
       const uint64_t n = std::min<uint64_t>(pl.per, cnt - o);
-      if (int rc = group(p, L, nb, K, party, cwb, s0s, k0, nk, range_add(A.x, off + o), n, pl.h, buf_bytes,
+      if (int rc = group(p, L, kb, party, s0s, k0, nk, range_add(A.x, off + o), n, pl.h, buf_bytes,
                          ys + ((k0 - key0) * row + (OUT::kFold ? 0 : o)) * 16, op.at(o)))
         return rc;
     }
@@ -2618,34 +2644,25 @@ static int range_wide(dcf_prg* p, Lease& L, const RangePlan& pl, size_t nb, size
                       uint8_t* ys, bool zero_blocks) {
   hipStream_t st = L.st;
   Workspace* w = L.w;
-  const uint32_t lam = (uint32_t)p->lambda, nlev = (uint32_t)(8 * nb);
+  const uint32_t lam = (uint32_t)p->lambda;
+  const KeyBlock kb(cwb, nb, lam, K);
   const RangeWideWs ws = pl.wide_ws(cnt);
-  if (w->dig_levels < pl.gkeys * nlev) {  // dig_levels stays the size of the buffer, as eval_wide_batch keeps it
-    size_t have = (size_t)w->dig_levels * 65;
-    if (int rc = grow(&w->d_dig, &have, (size_t)pl.gkeys * nlev * 65, st)) return rc;
-    w->dig_levels = (uint32_t)(pl.gkeys * nlev);
-  }
+  if (int rc = ensure_dig(w, pl.gkeys * kb.nlev, st)) return rc;
   if (int rc = range_begin(p, L, ws.total, zero_blocks)) return rc;
-  const uint8_t* cwv = cwb + (size_t)nlev * K * lam;
-  const uint8_t* cwt = cwb + 2 * (size_t)nlev * K * lam;
-  // CW digest of nk keys, key-major, dig_t behind their rows: bytes [0,32) of each level's cw_s / cw_v, and cw_t
-  const auto digest = [&](uint64_t k0, uint64_t nk) {
-    hipLaunchKernelGGL(k_cw_digest, dim3((unsigned)((4 * nlev * nk + 255) / 256)), dim3(256), 0, st, cwb, cwv, cwt, nlev,
-                       lam, (uint64_t)K, k0, (uint32_t)nk, (uint4*)w->d_dig, w->d_dig + (size_t)nk * nlev * 64);
-    return hipGetLastError();
-  };
   const bool once = nkeys == 1;  // a call's only key: its digest is built once, ahead of mark 1
-  if (once) HIP_TRY(digest(key0, 1));
+  if (once)
+    if (int rc = launch_digest(w, kb, key0, 1, st)) return rc;
   phase_mark(p, L, 1);
   const auto group =
       pl.per_lane ? (lam == 32 ? range_wide_group<true, RangeDigKeys> : range_wide_group<false, RangeDigKeys>)
                   : (lam == 32 ? range_wide_group<true, RangeOneKey> : range_wide_group<false, RangeOneKey>);
   for (uint64_t k0 = key0; k0 < key0 + nkeys; k0 += pl.gkeys) {
     const uint64_t nk = std::min<uint64_t>(pl.gkeys, key0 + nkeys - k0);
-    if (!once) HIP_TRY(digest(k0, nk));
+    if (!once)
+      if (int rc = launch_digest(w, kb, k0, nk, st)) return rc;
     for (uint64_t o = 0; o < cnt; o += pl.per) {  // several keys to a group, or h = 0: cnt <= per, one pass
       const uint64_t n = std::min<uint64_t>(pl.per, cnt - o);
-      if (int rc = group(p, L, nb, K, party, cwb, s0s, k0, nk, range_add(A.x, off + o), n, pl.h, ws,
+      if (int rc = group(p, L, kb, party, s0s, k0, nk, range_add(A.x, off + o), n, pl.h, ws,
                          ys + ((k0 - key0) * cnt + o) * lam))
         return rc;
     }
@@ -2657,9 +2674,9 @@ static int range_wide(dcf_prg* p, Lease& L, const RangePlan& pl, size_t nb, size
 // zeroed the key's padding).
 static int range_gather(dcf_prg* p, Lease& L, size_t nb, size_t K, uint64_t k, const uint8_t* cwb, const uint8_t* s0s,
                         uint8_t* dk, uint8_t* ds0) {
-  const size_t lam = p->lambda;
-  hipLaunchKernelGGL(k_rangemk_gather, dim3(8), dim3(256), 0, L.st, cwb, cwb + dcf_cwb_np1_offset(nb, lam, K), s0s,
-                     (uint64_t)K, k, (uint32_t)(8 * nb), (uint32_t)lam, (uint32_t)dcf_cwb_np1_offset(nb, lam, 1), dk, ds0);
+  const KeyBlock src(cwb, nb, p->lambda, K), dst(dk, nb, p->lambda, 1);
+  hipLaunchKernelGGL(k_rangemk_gather, dim3(8), dim3(256), 0, L.st, cwb, src.np1, s0s, src.K, k, src.nlev, src.lam,
+                     (uint32_t)(dst.np1 - dk), dk, ds0);
   HIP_TRY(hipGetLastError());
   return DCF_OK;
 }
@@ -2739,12 +2756,9 @@ static int full_domain_mmo16(dcf_prg* p, Lease& L, size_t n_bytes, int party, co
                              uint8_t* ys) {
   hipStream_t st = L.st;
   const uint32_t nlev = (uint32_t)(8 * n_bytes);
-  const size_t lam = 16, nodeb = 33;
+  const size_t nodeb = 33;
   const uint64_t maxnodes = (1ull << nlev) / 2;
-  const uint4* cws = (const uint4*)cwb;
-  const uint4* cwv = (const uint4*)(cwb + nlev * lam);
-  const uint8_t* cwt = cwb + 2 * nlev * lam;
-  const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(n_bytes, lam, 1));
+  const KeyBlock kb(cwb, n_bytes, 16, 1);
   // + one work counter per launch (64-node units, see next_wave_base) after the nodes
   const size_t ctr_off = (2 * maxnodes * nodeb + 64 + 255) & ~(size_t)255;
   if (int rc = ensure_ws(L.w, ctr_off + 64 * sizeof(uint32_t), st)) return rc;
@@ -2762,8 +2776,8 @@ static int full_domain_mmo16(dcf_prg* p, Lease& L, size_t n_bytes, int party, co
   for (uint32_t lev = 0; lev < nlev; ++lev) {
     const uint64_t parents = 1ull << lev;
     hipLaunchKernelGGL(k_fd_level16_mmo, dim3((unsigned)grid_for(parents, p->cus)), dim3(kBlock), 0, st, p->d_tab,
-                       p->d_rk128, cws, cwv, cwt, np1, lev, nlev, parents, s_a, v_a, t_a, s_b, v_b, t_b, (uint4*)ys,
-                       ctrs + lev);
+                       p->d_rk128, kb.s4(), kb.v4(), kb.cwt, kb.np14(), lev, nlev, parents, s_a, v_a, t_a, s_b, v_b, t_b,
+                       (uint4*)ys, ctrs + lev);
     HIP_TRY(hipGetLastError());
     std::swap(s_a, s_b);
     std::swap(v_a, v_b);
@@ -2793,19 +2807,16 @@ int dcf_eval_full_domain_device(dcf_prg* p, size_t n_bytes, int party, const uin
   const size_t lam = p->lambda;
   if (p->kind == 0 && lam == 16 && nlev >= kFdTail + 12) {
     const uint32_t lev_end = nlev - kFdTail;
-    const uint4* cws = (const uint4*)cwb;
-    const uint4* cwv = (const uint4*)(cwb + nlev * lam);
-    const uint8_t* cwt = cwb + 2 * nlev * lam;
-    const uint4* np1 = (const uint4*)(cwb + dcf_cwb_np1_offset(n_bytes, lam, 1));
+    const KeyBlock kb(cwb, n_bytes, lam, 1);
     PrefixTable pf{nullptr, 0u};
-    const int brc = build_prefix(p, L.w, party, cws, cwv, cwt, np1, s0, lev_end, &pf, st);
+    const int brc = build_prefix(p, L.w, party, kb, s0, lev_end, &pf, st);
     if (brc != DCF_OK && brc != kPrefixNoMem) return brc;
     if (brc == DCF_OK) {
       const uint64_t nodes = 1ull << lev_end;
       if (int rc2 = ensure_ctr(L.w)) return rc2;
       HIP_TRY(hipMemsetAsync(L.w->d_ctr, 0, kCtrBytes, st));
       hipLaunchKernelGGL(k_fd_dfs16<kFdTail>, dim3((unsigned)grid_for(nodes, p->cus)), dim3(kBlock), 0, st, p->d_tab,
-                         p->rk[0], cws, cwv, cwt, np1, lev_end, nodes, pf.sv, (uint4*)ys, L.w->d_ctr);
+                         p->rk[0], kb.s4(), kb.v4(), kb.cwt, kb.np14(), lev_end, nodes, pf.sv, (uint4*)ys, L.w->d_ctr);
       HIP_TRY(hipGetLastError());
       return DCF_OK;
     }
@@ -2846,9 +2857,8 @@ static int host_range(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t*
 int dcf_eval_range(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, size_t cwb_len, const uint8_t* s0,
                    const uint8_t* x0, uint64_t count, uint8_t* ys, size_t ys_len) {
   if (int rc = RangeCall::check(p, n_bytes, party, cwb, s0, x0)) return rc;
+  if (int rc = check_host_key(false, n_bytes, party, p, cwb_len)) return rc;  // (the key's size: the rest is checked)
   const size_t lam = p->lambda;
-  if (cwb_len != dcf_cwb_bytes(n_bytes, lam, 1))
-    return fail(DCF_ERR_KEY, "key size does not match 8*N levels (lib.rs:165)");
   if (ys_len % lam != 0 || ys_len / lam != count) return fail(DCF_ERR_LEN, "ys length != count * lambda");
   if (count == 0) return DCF_OK;
   if (!ys) return fail(DCF_ERR_ARG, "null buffer");
@@ -2980,43 +2990,23 @@ int dcf_gen(dcf_prg* p, size_t n_bytes, const uint8_t* alpha, const uint8_t* bet
   if (!p || !alpha || !beta || !s0_0 || !s0_1 || !cwb_out) return fail(DCF_ERR_ARG, "null argument");
   if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
   if (bound != DCF_BOUND_LT_BETA && bound != DCF_BOUND_GT_BETA) return fail(DCF_ERR_ARG, "bad bound");
-  DeviceGuard dg(p->device);
-  if (!dg.ok) return fail(DCF_ERR_HIP, "hipSetDevice failed");
-  Lease L(p);
-  int rc = host_lease(L);
-  if (rc == DCF_OK) rc = host_gen(p, L, n_bytes, alpha, beta, s0_0, s0_1, bound, cwb_out);
-  return host_finish(L, rc);
+  return host_call(p, [&](Lease& L) { return host_gen(p, L, n_bytes, alpha, beta, s0_0, s0_1, bound, cwb_out); });
 }
 
 int dcf_eval(dcf_prg* p, size_t n_bytes, int party, const uint8_t* cwb, size_t cwb_len, const uint8_t* s0,
              const uint8_t* xs, size_t m, uint8_t* ys, size_t ys_len) {
-  if (!p || !cwb || !s0) return fail(DCF_ERR_ARG, "null argument");
-  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
-  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
-  const size_t lam = p->lambda;
-  if (cwb_len != dcf_cwb_bytes(n_bytes, lam, 1))
-    return fail(DCF_ERR_KEY, "key size does not match 8*N levels (lib.rs:165)");
-  if (ys_len != m * lam) return fail(DCF_ERR_LEN, "ys length != m * lambda");
+  if (int rc = check_host_key(!p || !cwb || !s0, n_bytes, party, p, cwb_len)) return rc;
+  if (ys_len != m * p->lambda) return fail(DCF_ERR_LEN, "ys length != m * lambda");
   if (m == 0) return DCF_OK;
   if (!xs || !ys) return fail(DCF_ERR_ARG, "null buffer");
-  DeviceGuard dg(p->device);
-  if (!dg.ok) return fail(DCF_ERR_HIP, "hipSetDevice failed");
-  Lease L(p);
-  int rc = host_lease(L);
-  if (rc == DCF_OK) rc = host_eval(p, L, n_bytes, party, cwb, cwb_len, s0, xs, m, ys);
-  return host_finish(L, rc);
+  return host_call(p, [&](Lease& L) { return host_eval(p, L, n_bytes, party, cwb, cwb_len, s0, xs, m, ys); });
 }
 
 int dcf_prg_gen(dcf_prg* p, const uint8_t* seeds, size_t m, uint8_t* out) {
   if (!p) return fail(DCF_ERR_ARG, "null prg");
   if (m == 0) return DCF_OK;
   if (!seeds || !out) return fail(DCF_ERR_ARG, "null buffer");
-  DeviceGuard dg(p->device);
-  if (!dg.ok) return fail(DCF_ERR_HIP, "hipSetDevice failed");
-  Lease L(p);
-  int rc = host_lease(L);
-  if (rc == DCF_OK) rc = host_prg_gen(p, L, seeds, m, out);
-  return host_finish(L, rc);
+  return host_call(p, [&](Lease& L) { return host_prg_gen(p, L, seeds, m, out); });
 }
 
 // ---- multi-GPU (SURVEY §8(b) dcf_eval_multi_gpu; the reference spreads Dcf::eval over
@@ -3038,12 +3028,8 @@ static int check_group(dcf_prg* const* prgs, size_t G) {
 int dcf_eval_multi_gpu(dcf_prg* const* prgs, size_t G, size_t n_bytes, int party, const uint8_t* cwb,
                        size_t cwb_len, const uint8_t* s0, const uint8_t* xs, size_t m, uint8_t* ys, size_t ys_len) {
   if (int rc = check_group(prgs, G)) return rc;
-  if (!cwb || !s0) return fail(DCF_ERR_ARG, "null argument");
-  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
-  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
+  if (int rc = check_host_key(!cwb || !s0, n_bytes, party, prgs[0], cwb_len)) return rc;
   const size_t lam = prgs[0]->lambda;
-  if (cwb_len != dcf_cwb_bytes(n_bytes, lam, 1))
-    return fail(DCF_ERR_KEY, "key size does not match 8*N levels (lib.rs:165)");
   if (ys_len != m * lam) return fail(DCF_ERR_LEN, "ys length != m * lambda");
   if (m == 0) return DCF_OK;
   if (!xs || !ys) return fail(DCF_ERR_ARG, "null buffer");
@@ -3053,16 +3039,9 @@ int dcf_eval_multi_gpu(dcf_prg* const* prgs, size_t G, size_t n_bytes, int party
     size_t start, cnt;
     dcf_point_slice(m, G, g, &start, &cnt);
     if (cnt == 0) return;
-    DeviceGuard dg(prgs[g]->device);
-    if (!dg.ok) {
-      rcs[g] = fail(DCF_ERR_HIP, "hipSetDevice failed");
-    } else {
-      Lease L(prgs[g]);
-      int rc = host_lease(L);
-      if (rc == DCF_OK)
-        rc = host_eval(prgs[g], L, n_bytes, party, cwb, cwb_len, s0, xs + start * n_bytes, cnt, ys + start * lam);
-      rcs[g] = host_finish(L, rc);
-    }
+    rcs[g] = host_call(prgs[g], [&](Lease& L) {
+      return host_eval(prgs[g], L, n_bytes, party, cwb, cwb_len, s0, xs + start * n_bytes, cnt, ys + start * lam);
+    });
     if (rcs[g]) errs[g] = t_err;
   };
   std::vector<std::thread> th;
@@ -3078,12 +3057,8 @@ int dcf_eval_multi_gpu_device(dcf_prg* const* prgs, size_t G, size_t n_bytes, in
                               size_t cwb_len, const uint8_t* s0, const uint8_t* const* xs, const size_t* ms,
                               uint8_t* const* ys, void* const* streams, uint8_t* gather_ys) {
   if (int rc = check_group(prgs, G)) return rc;
-  if (!cwb || !s0 || !xs || !ms || !ys) return fail(DCF_ERR_ARG, "null argument");
-  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
-  if (party != 0 && party != 1) return fail(DCF_ERR_ARG, "party must be 0 or 1");
+  if (int rc = check_host_key(!cwb || !s0 || !xs || !ms || !ys, n_bytes, party, prgs[0], cwb_len)) return rc;
   const size_t lam = prgs[0]->lambda;
-  if (cwb_len != dcf_cwb_bytes(n_bytes, lam, 1))
-    return fail(DCF_ERR_KEY, "key size does not match 8*N levels (lib.rs:165)");
   const int dev0 = prgs[0]->device;
   size_t off = 0;
   for (size_t g = 0; g < G; ++g) {

@@ -15,6 +15,8 @@ from .dcf import (  # noqa: F401
     DcfImpl,
     Engine,
     EvalPlan,
+    GenPlan,
+    GenRoute,
     MultiGpuDcf,
     Share,
     cwb_bytes,
@@ -25,6 +27,6 @@ from .dcf import (  # noqa: F401
 )
 
 __all__ = [
-    "Aes128MatyasMeyerOseasPrg", "Aes256HirosePrg", "BoundState", "CmpFn", "Cw", "DcfImpl", "Engine", "EvalPlan", "MultiGpuDcf", "Share", "point_slice", "DcfError",
+    "Aes128MatyasMeyerOseasPrg", "Aes256HirosePrg", "BoundState", "CmpFn", "Cw", "DcfImpl", "Engine", "EvalPlan", "GenPlan", "GenRoute", "MultiGpuDcf", "Share", "point_slice", "DcfError",
     "cwb_bytes", "cwb_np1_offset", "cwb_to_share", "share_to_cwb", "load", "LIB_PATH",
 ]

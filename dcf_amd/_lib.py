@@ -38,7 +38,7 @@ EXPORTS = [
     "dcf_eval_range_multikey_device", "dcf_eval_range_multikey_subtree_levels", "dcf_eval_range_keys_per_launch",
     "dcf_eval_range_wide_points_per_launch", "dcf_prefix_deepen_calls", "dcf_prefix_reuse_max_depth",
     "dcf_eval_range_wide_multikey_subtree_levels", "dcf_eval_range_wide_keys_per_launch",
-    "dcf_eval_range_fold_device", "dcf_eval_range_fold_multikey_device",
+    "dcf_eval_range_fold_device", "dcf_eval_range_fold_multikey_device", "dcf_gen_plan",
 ]
 
 
@@ -82,6 +82,8 @@ def load(path: str = LIB_PATH):
         "dcf_eval_prefix_levels": ([vp, sz, sz, sz], i),
         "dcf_eval_plan": ([vp, sz, sz, sz, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(i),
                            ctypes.POINTER(i)], i),
+        "dcf_gen_plan": ([vp, sz, sz, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(ctypes.c_uint64),
+                          ctypes.POINTER(i)], i),
         "dcf_eval_keys_per_launch": ([sz, sz], sz),
         "dcf_cwb_bytes": ([sz, sz, sz], sz),
         "dcf_cwb_np1_offset": ([sz, sz, sz], sz),

@@ -1197,7 +1197,7 @@ int eval_mmo_wide(dcf_prg* p, Workspace* w, const KeyBlock& kb, uint64_t key, in
 // Batched Dcf::gen with the MMO PRG at LAMBDA >= 32 (kernels_mmo_wide.h): per pass of keys,
 // the head over block 0 of both parties (t-CWs, per-level t bits), then the tail.
 int gen_mmo_wide(dcf_prg* p, Workspace* w, const KeyBlockOut& kb, const uint8_t* alpha, const uint8_t* beta,
-                 const uint8_t* s0_0, const uint8_t* s0_1, int bound, hipStream_t st) {
+                 const uint8_t* s0_0, const uint8_t* s0_1, int bound, bool tail, hipStream_t st) {
   const uint32_t lam = kb.lam, nb = lam / 16u, nlev = kb.nlev, n_bytes = nlev / 8;
   const uint64_t K = kb.K;
   uint8_t *cws = kb.cws, *cwv = kb.cwv, *cwt = kb.cwt, *np1 = kb.np1;
@@ -1208,7 +1208,7 @@ int gen_mmo_wide(dcf_prg* p, Workspace* w, const KeyBlockOut& kb, const uint8_t*
   hipLaunchKernelGGL(k_mmo_wide_gen<true>, gh, dim3(kBlock), 0, st, p->d_tab, p->d_rk128, alpha, beta, s0_0, s0_1,
                      (uint32_t)bound, (uint32_t)n_bytes, lam, K, cws, cwv, cwt, np1, tinfo);
   HIP_TRY(hipGetLastError());
-  if (nb > 1) {
+  if (tail) {  // blocks past the first (plan_gen: the call's second launch)
     const uint64_t items = groups * (nb - 1);
     const dim3 gt((unsigned)std::min<uint64_t>((items + 15) / 16, 4 * (uint64_t)p->cus));
     hipLaunchKernelGGL(k_mmo_wide_gen<false>, gt, dim3(kBlock), 0, st, p->d_tab, p->d_rk128, alpha, beta, s0_0,
@@ -1528,6 +1528,9 @@ int dcf_prg_trim(dcf_prg* p) {
   return (int)idle.size();
 }
 
+// Tiny host calls (the latency kernels' batch sizes): inputs and outputs through one pinned,
+// device-mapped buffer that the kernel reads and writes itself — one launch, no copy commands.
+constexpr size_t kTinyBytes = 1ull << 20;
 // Small gen batches run the latency kernels of kernels_lat.h as well (eval's thresholds: plan_eval).
 constexpr uint64_t kGenRowMax = 2048;    // keys up to which gen runs k_gen16_row (one wave per key; pipelined, r03t3:
                                          // 2048 keys 110 vs 148 us col, 4096 keys 149 vs 147, 8192 277 vs 165)
@@ -1538,79 +1541,152 @@ static uint32_t per_wg(uint64_t items, int cus, uint32_t cap) {
   const uint64_t per = (items + (uint64_t)cus - 1) / (uint64_t)cus;
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cap, per));
 }
-static bool col_gen(const dcf_prg* p, size_t n_bytes, uint64_t num_keys) {
-  return p->kind == 0 && p->lambda == 16 && num_keys <= kGenColMax && 8 * n_bytes <= kColMaxLevels;
-}
+// ---- One plan per gen call: plan_gen() alone tests the gen path's thresholds;
+// gen_launch, host_gen and dcf_gen_plan read the plan ----
+enum class GenRoute {
+  Row, Col,    // Hirose LAMBDA = 16, 8N <= 256: k_gen16_row (one wave per key) / k_gen16_col (16 lanes per key)
+  Quad, Lane,  // Hirose LAMBDA = 16 otherwise: k_gen16<4> / k_gen16<1>
+  Mmo16,       // k_gen16_mmo
+  Wide,        // Hirose LAMBDA >= 32: k_gen_wide, one workgroup per key, kGenChunk keys per launch
+  MmoWide,     // MMO LAMBDA >= 32: k_mmo_wide_gen head, then its tail over the blocks past the first
+};
+struct GenPlan {
+  GenRoute route = GenRoute::Lane;
+  bool counter = false;   // Quad / Lane: 64-lane units come from the work counter (else a grid-stride loop)
+  uint64_t items = 0;     // Quad / Lane: lanes of the call (4 or 1 per key)
+  uint64_t chunk = 0;     // Wide: keys per launch (scratch rows of 3 * LAMBDA bytes)
+  uint64_t launches = 1;  // kernel launches of the call
+  // dcf_gen of this N passes through the mapped tiny buffer: what a lone key runs on a latency kernel
+  bool host_tiny = false;
+};
+// Where dcf_gen lays one key's inputs and CWB in its host / device buffer pair (256-byte aligned parts).
+struct GenStage {
+  size_t oa, ob, o0, o1, ok, cwb_len, total;
+  GenStage(size_t nb, size_t lam)
+      : oa(0), ob(align256(nb)), o0(ob + align256(lam)), o1(o0 + align256(lam)), ok(o1 + align256(lam)),
+        cwb_len(dcf_cwb_bytes(nb, lam, 1)), total(ok + align256(cwb_len)) {}
+};
 
-static int gen_launch(dcf_prg* p, Lease& L, size_t n_bytes, size_t num_keys, const uint8_t* alpha,
-                      const uint8_t* beta, const uint8_t* s0_0, const uint8_t* s0_1, int bound, uint8_t* cwb_out) {
-  Workspace* w = L.w;
-  hipStream_t st = L.st;
+static GenPlan plan_gen(const dcf_prg* p, size_t n_bytes, uint64_t num_keys) {
+  GenPlan pl;
   const size_t lam = p->lambda;
-  const KeyBlockOut kb(cwb_out, n_bytes, lam, num_keys);
-  uint8_t *cws = kb.cws, *cwv = kb.cwv, *cwt = kb.cwt, *np1 = kb.np1;
-  if (p->kind == 1 && lam > 16) return gen_mmo_wide(p, w, kb, alpha, beta, s0_0, s0_1, bound, st);
-  if (p->kind == 1) {  // Aes128MatyasMeyerOseasPrg (LAMBDA = 16)
-    hipLaunchKernelGGL(k_gen16_mmo, dim3((unsigned)grid_for(num_keys, p->cus)), dim3(kBlock), 0, st, p->d_tab,
-                       p->d_rk128, alpha, (const uint4*)beta, (const uint4*)s0_0, (const uint4*)s0_1, (uint32_t)bound,
-                       (uint32_t)n_bytes, (uint64_t)num_keys, (uint4*)cws, (uint4*)cwv, cwt, (uint4*)np1);
-    HIP_TRY(hipGetLastError());
-    return DCF_OK;
+  const bool col = p->kind == 0 && lam == 16 && 8 * n_bytes <= kColMaxLevels;  // the latency kernels' shapes
+  pl.host_tiny = col && GenStage(n_bytes, lam).total <= kTinyBytes;
+  if (p->kind == 1) {
+    pl.route = lam > 16 ? GenRoute::MmoWide : GenRoute::Mmo16;
+    if (pl.route == GenRoute::MmoWide) pl.launches = lam / 16 > 1 ? 2 : 1;
+    return pl;
   }
-  if (lam > 16) {  // one workgroup per key, keys in chunks (scratch 3*LAMBDA per key)
-    const uint64_t chunk = num_keys < kGenChunk ? num_keys : kGenChunk;
-    int rc = ensure_ws(w, chunk * 3 * lam, st);
-    if (rc) return rc;
-    for (uint64_t k0 = 0; k0 < num_keys; k0 += chunk) {
-      const uint64_t cnt = (num_keys - k0 < chunk) ? num_keys - k0 : chunk;
-      hipLaunchKernelGGL(k_gen_wide, dim3((unsigned)cnt), dim3(kBlock), 0, st, p->d_tab, p->d_rk2, alpha,
-                         beta, s0_0, s0_1, (uint32_t)bound, (uint32_t)n_bytes, (uint64_t)num_keys, k0, (uint32_t)lam,
-                         cws, cwv, cwt, np1, w->d_ws);
-      HIP_TRY(hipGetLastError());
-    }
-    return DCF_OK;
+  if (lam > 16) {  // keys in chunks (scratch 3 * LAMBDA per key)
+    pl.route = GenRoute::Wide;
+    pl.chunk = num_keys < kGenChunk ? num_keys : kGenChunk;
+    pl.launches = pl.chunk ? (num_keys + pl.chunk - 1) / pl.chunk : 0;
+    return pl;
   }
-  if (col_gen(p, n_bytes, num_keys) && num_keys <= kGenRowMax) {
-    // The smallest batches: one wave per key, one table lookup per lane and AES round
-    // (k_gen16_row: a lone key's level is one 16-lane AES chain).
-    const uint32_t kpw = per_wg(num_keys, p->cus, kBlock / 64);
-    hipLaunchKernelGGL(k_gen16_row, dim3((unsigned)((num_keys + kpw - 1) / kpw)), dim3(kBlock), 0, st, p->d_tab,
-                       p->rk[0], alpha, beta, s0_0, s0_1, (uint32_t)bound, (uint32_t)n_bytes, kpw,
-                       (uint64_t)num_keys, cws, cwv, cwt, np1);
-    HIP_TRY(hipGetLastError());
-    return DCF_OK;
-  }
-  if (col_gen(p, n_bytes, num_keys)) {
-    // Small batches (a single key through the C ABI: benches/dcf.rs bench_gen) are latency-
-    // bound: 16 lanes per key, one AES column each (k_gen16_col).
-    const uint32_t kpw = per_wg(num_keys, p->cus, kBlock / 16);
-    hipLaunchKernelGGL(k_gen16_col, dim3((unsigned)((num_keys + kpw - 1) / kpw)), dim3(kBlock), 0, st, p->d_tab,
-                       p->rk[0], alpha, beta, s0_0, s0_1, (uint32_t)bound, (uint32_t)n_bytes, kpw,
-                       (uint64_t)num_keys, cws, cwv, cwt, np1);
-    HIP_TRY(hipGetLastError());
-    return DCF_OK;
+  if (col && num_keys <= kGenColMax) {
+    // The smallest batches: one wave per key, one table lookup per lane and AES round (a lone key's
+    // level is one 16-lane AES chain).  Small batches (a single key through the C ABI: benches/dcf.rs
+    // bench_gen) are latency-bound: 16 lanes per key, one AES column each.
+    pl.route = num_keys <= kGenRowMax ? GenRoute::Row : GenRoute::Col;
+    return pl;
   }
   // Large batches: 64-lane units from the work counter (waves drift apart, as in k_eval16).
   // Lanes per key: a quad while the batch leaves lanes idle (a key's 8N levels take a quarter of
   // the AES latency: single gen 826 -> 266 us), one lane per key for large batches (2^20 keys:
   // 7.5-7.6 ms with one lane, 8.0 with quads — the four lanes repeat the level update).
-  const bool quad = (uint64_t)num_keys <= (uint64_t)p->cus * kBlock / 2;
-  const uint64_t items = (uint64_t)num_keys * (quad ? 4u : 1u);
-  uint32_t* ctr = nullptr;
-  if (items >= (uint64_t)p->cus * kBlock * 2 && (items + 63) / 64 <= 0xFFFFFFFFull) {
-    if (int rc = ensure_ctr(w)) return rc;
-    HIP_TRY(hipMemsetAsync(w->d_ctr, 0, kCtrBytes, st));
-    ctr = w->d_ctr;
+  const bool quad = num_keys <= (uint64_t)p->cus * kBlock / 2;
+  pl.route = quad ? GenRoute::Quad : GenRoute::Lane;
+  pl.items = num_keys * (quad ? 4u : 1u);
+  pl.counter = pl.items >= (uint64_t)p->cus * kBlock * 2 && (pl.items + 63) / 64 <= 0xFFFFFFFFull;
+  return pl;
+}
+
+// The public image of GenRoute (include/dcf_hip.h); no default: a new GenRoute value fails to compile here.
+static int public_gen_route(GenRoute r) {
+  switch (r) {
+    case GenRoute::Row: return DCF_GEN_ROW;
+    case GenRoute::Col: return DCF_GEN_COL;
+    case GenRoute::Quad: return DCF_GEN_QUAD;
+    case GenRoute::Lane: return DCF_GEN_LANE;
+    case GenRoute::Mmo16: return DCF_GEN_MMO16;
+    case GenRoute::Wide: return DCF_GEN_WIDE;
+    case GenRoute::MmoWide: return DCF_GEN_MMO_WIDE;
   }
-  // Round keys in SGPRs (22 / 26 SGPR spills into VGPR lanes in the one-lane / quad instances):
-  // per-round keys from the device copy spill none but gen ran 1-1.5 % slower (C5 r05l).
-#define DCF_GEN16(LN)                                                                                           \
-  hipLaunchKernelGGL(k_gen16<LN>, dim3((unsigned)grid_for(items, p->cus)), dim3(kBlock), 0, st, p->d_tab, p->rk[0], \
-                     alpha, (const uint4*)beta, (const uint4*)s0_0, (const uint4*)s0_1, (uint32_t)bound,          \
+  return -1;
+}
+
+int dcf_gen_plan(const dcf_prg* p, size_t n_bytes, size_t num_keys, int* route, int* counter, uint64_t* launches,
+                 int* host_tiny) {
+  if (!p) return fail(DCF_ERR_ARG, "null prg");
+  if (n_bytes == 0) return fail(DCF_ERR_N, "n_bytes must be > 0");
+  const GenPlan pl = plan_gen(p, n_bytes, num_keys);
+  if (route) *route = public_gen_route(pl.route);
+  if (counter) *counter = pl.counter ? 1 : 0;
+  if (launches) *launches = pl.launches;
+  if (host_tiny) *host_tiny = pl.host_tiny ? 1 : 0;
+  return DCF_OK;
+}
+
+static int gen_launch(dcf_prg* p, Lease& L, const GenPlan& plan, size_t n_bytes, size_t num_keys,
+                      const uint8_t* alpha, const uint8_t* beta, const uint8_t* s0_0, const uint8_t* s0_1, int bound,
+                      uint8_t* cwb_out) {
+  Workspace* w = L.w;
+  hipStream_t st = L.st;
+  const size_t lam = p->lambda;
+  const KeyBlockOut kb(cwb_out, n_bytes, lam, num_keys);
+  uint8_t *cws = kb.cws, *cwv = kb.cwv, *cwt = kb.cwt, *np1 = kb.np1;
+  switch (plan.route) {
+    case GenRoute::MmoWide: return gen_mmo_wide(p, w, kb, alpha, beta, s0_0, s0_1, bound, plan.launches > 1, st);
+    case GenRoute::Mmo16:  // Aes128MatyasMeyerOseasPrg (LAMBDA = 16)
+      hipLaunchKernelGGL(k_gen16_mmo, dim3((unsigned)grid_for(num_keys, p->cus)), dim3(kBlock), 0, st, p->d_tab,
+                         p->d_rk128, alpha, (const uint4*)beta, (const uint4*)s0_0, (const uint4*)s0_1, (uint32_t)bound,
+                         (uint32_t)n_bytes, (uint64_t)num_keys, (uint4*)cws, (uint4*)cwv, cwt, (uint4*)np1);
+      break;
+    case GenRoute::Wide: {  // one workgroup per key
+      if (int rc = ensure_ws(w, plan.chunk * 3 * lam, st)) return rc;
+      for (uint64_t k0 = 0; k0 < num_keys; k0 += plan.chunk) {
+        const uint64_t cnt = (num_keys - k0 < plan.chunk) ? num_keys - k0 : plan.chunk;
+        hipLaunchKernelGGL(k_gen_wide, dim3((unsigned)cnt), dim3(kBlock), 0, st, p->d_tab, p->d_rk2, alpha,
+                           beta, s0_0, s0_1, (uint32_t)bound, (uint32_t)n_bytes, (uint64_t)num_keys, k0, (uint32_t)lam,
+                           cws, cwv, cwt, np1, w->d_ws);
+        HIP_TRY(hipGetLastError());
+      }
+      return DCF_OK;
+    }
+    case GenRoute::Row: {
+      const uint32_t kpw = per_wg(num_keys, p->cus, kBlock / 64);
+      hipLaunchKernelGGL(k_gen16_row, dim3((unsigned)((num_keys + kpw - 1) / kpw)), dim3(kBlock), 0, st, p->d_tab,
+                         p->rk[0], alpha, beta, s0_0, s0_1, (uint32_t)bound, (uint32_t)n_bytes, kpw,
+                         (uint64_t)num_keys, cws, cwv, cwt, np1);
+      break;
+    }
+    case GenRoute::Col: {
+      const uint32_t kpw = per_wg(num_keys, p->cus, kBlock / 16);
+      hipLaunchKernelGGL(k_gen16_col, dim3((unsigned)((num_keys + kpw - 1) / kpw)), dim3(kBlock), 0, st, p->d_tab,
+                         p->rk[0], alpha, beta, s0_0, s0_1, (uint32_t)bound, (uint32_t)n_bytes, kpw,
+                         (uint64_t)num_keys, cws, cwv, cwt, np1);
+      break;
+    }
+    case GenRoute::Quad:
+    case GenRoute::Lane: {
+      uint32_t* ctr = nullptr;
+      if (plan.counter) {
+        if (int rc = ensure_ctr(w)) return rc;
+        HIP_TRY(hipMemsetAsync(w->d_ctr, 0, kCtrBytes, st));
+        ctr = w->d_ctr;
+      }
+      // Round keys in SGPRs (22 / 26 SGPR spills into VGPR lanes in the one-lane / quad instances):
+      // per-round keys from the device copy spill none but gen ran 1-1.5 % slower (C5 r05l).
+#define DCF_GEN16(LN)                                                                                                  \
+  hipLaunchKernelGGL(k_gen16<LN>, dim3((unsigned)grid_for(plan.items, p->cus)), dim3(kBlock), 0, st, p->d_tab,         \
+                     p->rk[0], alpha, (const uint4*)beta, (const uint4*)s0_0, (const uint4*)s0_1, (uint32_t)bound,     \
                      (uint32_t)n_bytes, (uint64_t)num_keys, (uint4*)cws, (uint4*)cwv, cwt, (uint4*)np1, ctr)
-  if (quad) DCF_GEN16(4);
-  else DCF_GEN16(1);
+      if (plan.route == GenRoute::Quad) DCF_GEN16(4);
+      else DCF_GEN16(1);
 #undef DCF_GEN16
+      break;
+    }
+  }
   HIP_TRY(hipGetLastError());
   return DCF_OK;
 }
@@ -1625,7 +1701,7 @@ int dcf_gen_batch_device(dcf_prg* p, size_t n_bytes, size_t num_keys, const uint
   DeviceGuard dg(p->device);
   Lease L(p);
   if (int rc = L.order((hipStream_t)stream)) return rc;
-  return gen_launch(p, L, n_bytes, num_keys, alpha, beta, s0_0, s0_1, bound, cwb_out);
+  return gen_launch(p, L, plan_gen(p, n_bytes, num_keys), n_bytes, num_keys, alpha, beta, s0_0, s0_1, bound, cwb_out);
 }
 
 // ---- Dcf::eval: one function per engine of the plan; first the A/B knobs of eval_stream's instance ladder ----
@@ -1976,9 +2052,6 @@ int dcf_eval_multikey_device(dcf_prg* p, size_t n_bytes, size_t num_keys, size_t
 // Points per chunk of the host eval pipeline: ~128 MiB of x + y per buffer (C3 shape: 4 Mi
 // points, an 8 ms kernel against ~3 ms of PCIe each way, so the copies hide behind it).
 constexpr size_t kHostChunkBytes = 128ull << 20;
-// Tiny host calls (the latency kernels' batch sizes): inputs and outputs through one pinned,
-// device-mapped buffer that the kernel reads and writes itself — one launch, no copy commands.
-constexpr size_t kTinyBytes = 1ull << 20;
 constexpr size_t kHostMidBytes = 64ull << 20;  // x + y of a mid-size host eval through the mapped buffer
 
 static int ensure_host_path(Workspace* w) {
@@ -2186,10 +2259,11 @@ static int host_eval(dcf_prg* p, Lease& L, size_t nb, int party, const uint8_t* 
 static int host_gen(dcf_prg* p, Lease& L, size_t nb, const uint8_t* alpha, const uint8_t* beta, const uint8_t* s0_0,
                     const uint8_t* s0_1, int bound, uint8_t* cwb_out) {
   Workspace* w = L.w;
-  const size_t lam = p->lambda, cwb_len = dcf_cwb_bytes(nb, lam, 1);
-  const size_t oa = 0, ob = align256(nb), o0 = ob + align256(lam), o1 = o0 + align256(lam), ok = o1 + align256(lam);
-  const size_t total = ok + align256(cwb_len);
-  const bool tiny = col_gen(p, nb, 1) && total <= kTinyBytes;
+  const size_t lam = p->lambda;
+  const GenStage g(nb, lam);
+  const size_t oa = g.oa, ob = g.ob, o0 = g.o0, o1 = g.o1, ok = g.ok, cwb_len = g.cwb_len, total = g.total;
+  const GenPlan plan = plan_gen(p, nb, 1);
+  const bool tiny = plan.host_tiny;
   uint8_t *h = nullptr, *d = nullptr;
   if (tiny) {
     if (int rc = ensure_tiny(w, &d)) return rc;
@@ -2206,7 +2280,7 @@ static int host_gen(dcf_prg* p, Lease& L, size_t nb, const uint8_t* alpha, const
   hipStream_t sc = L.st;
   if (!tiny) HIP_TRY(hipMemcpyAsync(d, h, ok, hipMemcpyHostToDevice, sc));
   if (!tiny) HIP_TRY(hipMemsetAsync(d + ok, 0, cwb_len, sc));  // the CWB's padding bytes read 0
-  int rc = gen_launch(p, L, nb, 1, d + oa, d + ob, d + o0, d + o1, bound, d + ok);
+  int rc = gen_launch(p, L, plan, nb, 1, d + oa, d + ob, d + o0, d + o1, bound, d + ok);
   if (rc) return rc;
   if (!tiny) HIP_TRY(hipMemcpyAsync(h + ok, d + ok, cwb_len, hipMemcpyDeviceToHost, sc));
   HIP_TRY(hipStreamSynchronize(sc));

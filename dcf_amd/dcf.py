@@ -65,6 +65,25 @@ class EvalPlan(NamedTuple):
     unsupported: Optional[str] = None
 
 
+class GenRoute(enum.IntEnum):
+    """`dcf_gen_route` of include/dcf_hip.h: the kernel family a gen call runs."""
+    ROW = 0
+    COL = 1
+    QUAD = 2
+    LANE = 3
+    MMO16 = 4
+    WIDE = 5
+    MMO_WIDE = 6
+
+
+class GenPlan(NamedTuple):
+    """`dcf_gen_plan`: what a gen call of a shape decides before it launches anything."""
+    route: GenRoute
+    counter: bool
+    launches: int
+    host_tiny: bool
+
+
 @dataclass
 class CmpFn:
     """lib.rs:41-46: alpha (N bytes), beta (LAMBDA bytes)."""
@@ -234,6 +253,14 @@ class Aes256HirosePrg:
         else:
             check(rc)
         return EvalPlan(Engine(e.value), int(k.value), int(d.value), bool(s.value), why)
+
+    def gen_plan(self, n_bytes: int, num_keys: int = 1) -> GenPlan:
+        """The kernel route, work-counter flag and launch count of a gen of `num_keys` keys, and
+        whether `DcfImpl.gen` of this N uses the mapped tiny buffer (dcf_gen_plan; nothing is launched)."""
+        r, c, n, t = ctypes.c_int(-1), ctypes.c_int(), ctypes.c_uint64(), ctypes.c_int()
+        check(_lib.load().dcf_gen_plan(self._h, int(n_bytes), int(num_keys), ctypes.byref(r), ctypes.byref(c),
+                                       ctypes.byref(n), ctypes.byref(t)))
+        return GenPlan(GenRoute(r.value), bool(c.value), int(n.value), bool(t.value))
 
     @staticmethod
     def prefix_deepen_calls(depth: int, points: int) -> int:

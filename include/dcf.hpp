@@ -254,6 +254,21 @@ class DcfImpl final : public Dcf<N, LAMBDA> {
     return EvalPlan{(dcf_engine)e, k, d, s != 0, rc == DCF_OK ? std::string() : std::string(dcf_last_error())};
   }
 
+  // What a gen of num_keys keys on `prg` decides before it launches anything (dcf_gen_plan); host_tiny:
+  // whether gen() of this N passes through the mapped tiny buffer.
+  struct GenPlan {
+    dcf_gen_route route;
+    bool counter;
+    uint64_t launches;
+    bool host_tiny;
+  };
+  static GenPlan gen_plan(const PrgT& prg, size_t num_keys = 1) {
+    int r = 0, c = 0, t = 0;
+    uint64_t n = 0;
+    check(dcf_gen_plan(prg.handle(), N, num_keys, &r, &c, &n, &t));
+    return GenPlan{(dcf_gen_route)r, c != 0, n, t != 0};
+  }
+
   // Height of the aligned blocks eval_range expands for `count` points.
   static int range_subtree_levels(uint64_t count) { return dcf_eval_range_subtree_levels(N, count); }
   // Outputs per launch group of the Hirose LAMBDA >= 32 tree path of eval_range (0: not that path).

@@ -194,6 +194,31 @@ typedef enum dcf_engine {
  * null prg -> DCF_ERR_ARG, n_bytes == 0 -> DCF_ERR_N (outputs untouched). */
 int dcf_eval_plan(const dcf_prg* prg, size_t n_bytes, size_t num_keys, size_t points_per_key, int* engine,
                   int* key_mode, int* prefix_levels, int* small);
+/* The kernel family a gen call runs (dcf_gen_plan). */
+typedef enum dcf_gen_route {
+  DCF_GEN_ROW = 0,     /* Hirose, LAMBDA = 16, N <= 32, up to 2048 keys: one wave per key */
+  DCF_GEN_COL = 1,     /*   up to 16384 keys: 16 lanes per key */
+  DCF_GEN_QUAD = 2,    /* Hirose, LAMBDA = 16 otherwise: a lane quad per key up to compute units * 512 keys, */
+  DCF_GEN_LANE = 3,    /*   one lane per key beyond */
+  DCF_GEN_MMO16 = 4,   /* Aes128MatyasMeyerOseasPrg at LAMBDA = 16: one lane per key */
+  DCF_GEN_WIDE = 5,    /* Hirose, LAMBDA >= 32: one workgroup per key, launches of 4096 keys */
+  DCF_GEN_MMO_WIDE = 6 /* Aes128MatyasMeyerOseasPrg at LAMBDA >= 32: a head launch over block 0, a tail over the rest */
+} dcf_gen_route;
+/* The plan of a dcf_gen_batch_device call of num_keys keys (and of dcf_gen: num_keys = 1): what
+ * the call decides before it launches anything.  Pure arithmetic on the prg's configuration and
+ * its device's compute-unit count; nothing is launched.  Any of the four outputs may be NULL.
+ *   route      a dcf_gen_route, as listed above.
+ *   counter    1 when the QUAD or LANE route hands its 64-lane units out from a work counter: the
+ *              call has at least compute units * 2048 lanes (4 per key on QUAD, 1 on LANE); below
+ *              that, and on every other route, 0 (a grid-stride loop or a fixed grid).
+ *   launches   kernel launches of the call: ceil(num_keys / 4096) on WIDE, 2 on MMO_WIDE (1 if
+ *              LAMBDA were 16), 1 on every other route.
+ *   host_tiny  1 when dcf_gen of this N passes its inputs and the CWB through the mapped 1 MiB
+ *              buffer (one launch, no copy commands: the ROW / COL shapes) instead of the staged
+ *              copies; it does not depend on num_keys and is meaningful at num_keys = 1.
+ * null prg -> DCF_ERR_ARG, n_bytes == 0 -> DCF_ERR_N (outputs untouched). */
+int dcf_gen_plan(const dcf_prg* prg, size_t n_bytes, size_t num_keys, int* route, int* counter, uint64_t* launches,
+                 int* host_tiny);
 /* Keys per kernel launch of a LAMBDA = 16 multi-key stream eval (dcf_eval_multikey_device and
  * the host entry points with several keys): min(2^24, 2^31 / points_per_key, 2^30 / 8N), at
  * least 1 — the engine's point, work and CW-digest-row indices are 32-bit, so a larger call runs
@@ -296,9 +321,13 @@ int dcf_prg_gen(dcf_prg* prg, const uint8_t* seeds, size_t m, uint8_t* out);
 
 /* ---- device-pointer, asynchronous on `stream` ---- */
 
-/* Batched Dcf::gen: K independent keys, one GPU lane per key.
+/* Batched Dcf::gen: K independent keys (the kernel route: dcf_gen_plan).
  * alpha: K * n_bytes, beta / s0_0 / s0_1: K * lambda (row k = key k),
- * cwb_out: dcf_cwb_bytes(n_bytes, lambda, K). */
+ * cwb_out: dcf_cwb_bytes(n_bytes, lambda, K).
+ * beta, s0_0, s0_1 and cwb_out must be 16-byte aligned: the kernels read and write them as uint4.
+ * The call writes cw_s, cw_v, cw_t and cw_np1 and nothing else: the padding bytes between cw_t
+ * and cw_np1 ([2 * 8N * K * lambda + 8N * K, dcf_cwb_np1_offset)) keep what the buffer held.
+ * (dcf_gen returns them as zeros.) */
 int dcf_gen_batch_device(dcf_prg* prg, size_t n_bytes, size_t num_keys, const uint8_t* alpha, const uint8_t* beta,
                          const uint8_t* s0_0, const uint8_t* s0_1, int bound, uint8_t* cwb_out, void* stream);
 

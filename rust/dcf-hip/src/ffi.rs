@@ -29,6 +29,15 @@ pub const DCF_ENGINE_PAIR: c_int = 6;
 pub const DCF_ENGINE_STREAM: c_int = 7;
 pub const DCF_ENGINE_TTABLE: c_int = 8;
 
+/// `dcf_gen_route` of include/dcf_hip.h (the `route` output of `dcf_gen_plan`).
+pub const DCF_GEN_ROW: c_int = 0;
+pub const DCF_GEN_COL: c_int = 1;
+pub const DCF_GEN_QUAD: c_int = 2;
+pub const DCF_GEN_LANE: c_int = 3;
+pub const DCF_GEN_MMO16: c_int = 4;
+pub const DCF_GEN_WIDE: c_int = 5;
+pub const DCF_GEN_MMO_WIDE: c_int = 6;
+
 extern "C" {
     pub fn dcf_version() -> *const c_char;
     pub fn dcf_last_error() -> *const c_char;
@@ -45,6 +54,8 @@ extern "C" {
     pub fn dcf_eval_plan(prg: *const DcfPrg, n_bytes: usize, num_keys: usize, points_per_key: usize,
                          engine: *mut c_int, key_mode: *mut c_int, prefix_levels: *mut c_int,
                          small: *mut c_int) -> c_int;
+    pub fn dcf_gen_plan(prg: *const DcfPrg, n_bytes: usize, num_keys: usize, route: *mut c_int, counter: *mut c_int,
+                        launches: *mut u64, host_tiny: *mut c_int) -> c_int;
     pub fn dcf_eval_keys_per_launch(n_bytes: usize, points_per_key: usize) -> usize;
     pub fn dcf_prg_set_prefix_max_bytes(prg: *mut DcfPrg, max_bytes: usize) -> c_int;
     pub fn dcf_prefix_deepen_calls(depth: c_int, points: usize) -> u64;

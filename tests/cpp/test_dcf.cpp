@@ -142,6 +142,13 @@ int main() {
     CHECK(mk.engine == DCF_ENGINE_PAIR && mk.key_mode == 2);
     CHECK((dcf::DcfImpl<16, 16, decltype(mmo)>::eval_plan(mmo, 5, 64).engine == DCF_ENGINE_MMO16));
   }
+  {  // dcf_gen_plan: one key at N = 16 runs the wave-per-key kernel through the tiny buffer; 2049 keys the column kernel
+    const auto one = Dcf16::gen_plan(prg);
+    CHECK(one.route == DCF_GEN_ROW && !one.counter && one.launches == 1 && one.host_tiny);
+    CHECK(Dcf16::gen_plan(prg, 2049).route == DCF_GEN_COL);
+    const auto m = dcf::DcfImpl<16, 16, decltype(mmo)>::gen_plan(mmo, 5);
+    CHECK(m.route == DCF_GEN_MMO16 && !m.host_tiny);
+  }
   std::printf("%s (%d failures)\n", failures ? "FAILED" : "cpp mirror ok", failures);
   return failures ? 1 : 0;
 }

@@ -79,6 +79,14 @@ def test_argument_validation_without_gpu(hip_lib):
     assert b"cipher" in hip_lib.dcf_last_error() or hip_lib.dcf_last_error() != b""
     assert hip_lib.dcf_eval(None, 16, 0, None, 0, None, None, 0, None, 0) == -1
     assert hip_lib.dcf_gen_batch_device(None, 16, 1, None, None, None, None, 0, None, None) == -1
+    # dcf_gen_plan: null prg -> DCF_ERR_ARG; n_bytes == 0 -> DCF_ERR_N before the prg is read (a zeroed
+    # stand-in handle: no prg exists without a device); the outputs stay untouched
+    r, n = ctypes.c_int(-5), ctypes.c_uint64(77)
+    assert hip_lib.dcf_gen_plan(None, 16, 1, ctypes.byref(r), None, ctypes.byref(n), None) == -1
+    assert b"null prg" in hip_lib.dcf_last_error()
+    stand_in = ctypes.create_string_buffer(1 << 16)
+    assert hip_lib.dcf_gen_plan(ctypes.addressof(stand_in), 0, 1, ctypes.byref(r), None, ctypes.byref(n), None) == -4
+    assert b"n_bytes" in hip_lib.dcf_last_error() and r.value == -5 and n.value == 77
 
 
 def test_share_cwb_roundtrip_matches_oracle_layout(hip_lib):

@@ -7,6 +7,7 @@ import pytest
 
 from oracle import oracle as O
 from tests.golden.make_golden import REF_ALPHAS, REF_BETA, REF_KEYS, detbytes
+from tests.test_gen_dispatch_gpu import assert_key_is_oracle, cwb_parts
 
 pytestmark = pytest.mark.gpu
 
@@ -436,12 +437,11 @@ def test_wide_gen_batch_and_multikey(dcf):
     xs = _rand(rng, (K * Pp, nb))
     y1 = d.eval_multikey_device(True, cwb, T(s1), T(xs), Pp)
     torch.cuda.synchronize()
-    cw, y1h = cwb.cpu().numpy(), y1.cpu().numpy()
-    n = 8 * nb
-    cws = cw[:n * K * lam].reshape(n, K, lam)
+    y1h = y1.cpu().numpy()
+    parts = cwb_parts(dcf, cwb.cpu().numpy(), nb, lam, K)
     for key in range(K):
         ok = O.gen(Po, alpha[key].tobytes(), beta[key].tobytes(), s0[key].tobytes(), s1[key].tobytes(), 1)
-        assert np.array_equal(cws[:, key], ok.cw_s)
+        assert_key_is_oracle(parts, key, ok)  # cw_s, cw_v, cw_t and cw_np1
         sl = slice(key * Pp, (key + 1) * Pp)
         assert np.array_equal(y1h[sl], O.eval_(Po, 1, ok, s1[key].tobytes(), xs[sl]))
 
@@ -594,14 +594,12 @@ def test_gen_batch_large_counter_path(dcf, nb):
     y0 = d.eval_multikey_device(False, cwb, s0, xs, P)
     y1 = d.eval_multikey_device(True, cwb, s1, xs, P)
     torch.cuda.synchronize()
-    n = 8 * nb
-    cw = cwb.cpu().numpy()
-    cws = cw[:n * K * 16].reshape(n, K, 16)
+    parts = cwb_parts(dcf, cwb.cpu().numpy(), nb, 16, K)
     A, B, S0, S1, X = (t.cpu().numpy() for t in (alpha, beta, s0, s1, xs))
     Y0, Y1 = y0.cpu().numpy(), y1.cpu().numpy()
     for key in sorted(set([0, K - 1] + list(rng.integers(0, K, 24)))):
         ok = O.gen(Po, A[key].tobytes(), B[key].tobytes(), S0[key].tobytes(), S1[key].tobytes(), 0)
-        assert np.array_equal(cws[:, key], ok.cw_s), key
+        assert_key_is_oracle(parts, key, ok)  # cw_s, cw_v, cw_t and cw_np1
         assert np.array_equal(Y0[key:key + 1], O.eval_(Po, 0, ok, S0[key].tobytes(), X[key:key + 1]))
         assert np.array_equal(Y1[key:key + 1], O.eval_(Po, 1, ok, S1[key].tobytes(), X[key:key + 1]))
     # reconstruction on every key: y0 ^ y1 = beta * [x < alpha]
